@@ -9,7 +9,13 @@ kernel over all 4,999 windows.  Multi-GPU: one process per GPU (torchrun), each 
 own 50 Msite shard (its own seed), no collective on the data path (weak scaling); only the
 timing barrier and max-over-ranks reduction use torch.distributed.
 
-Prints one JSON line (rank 0).  `roofline` is for the dominant kernel (call_scan_kernel, the
+A plain run sets up, warms up, times --steps steps and prints one JSON line (rank 0) with the
+headline figure (`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed
+step computed as DIR/<name>.npy.  Everything else is measured or checked only with `--full`: the
+roofline and stage breakdown, the PCIe / streamed / command-line rates, the CPU baselines, the
+parity sample and the rows cross-check.
+
+With --full: `roofline` is for the dominant kernel (call_scan_kernel, the
 first kernel of the rows-only call): its algorithmic bytes per launch / its mean duration,
 measured with HIP events the library records on the stream the kernel runs on
 (pbg_set_kernel_timing / pbg_kernel_time).  `cpu_baseline` times the CPU oracle (C++ restatement of the reference
@@ -97,6 +103,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline figure: "
+                         "roofline and stage breakdown, PCIe / streamed / command-line rates, CPU baselines, parity "
+                         "sample, rows cross-check (the options below that size those legs apply only then)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64): every window output, and a fixed seeded sample of the packed rows and, when "
+                         "they are many, of the windows (under 64 MB in all)")
     ap.add_argument("--sites", type=int, default=50_000_000, help="positions per GPU")
     ap.add_argument("--samples", type=int, default=12)
     ap.add_argument("--depth", type=int, default=10)
@@ -135,6 +149,8 @@ def parse():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.chunk is None:
         # one chunk per 125 Mbp contig (~64 GB of keys in the one serial buffer) for configs[3]'s
         # serial pass, 2^25 when two buffers alternate (--overlap), 2^23 at configs[4]'s 96 samples
@@ -704,6 +720,64 @@ def zns_chain_floor(ld_snps, zns_ms: float | None = None) -> dict:
     return out
 
 
+DUMP_ROWS_BYTES = 8 << 20       # float32 bytes of the sampled rows (their float64 indices: at most as many)
+DUMP_WINDOWS_BYTES = 32 << 20   # float64 bytes of all window outputs together
+
+
+def spread_sample(n: int, k: int, seed: int):
+    """k of range(n), ascending and distinct, one drawn in each of k equal strata: fixed by
+    (n, k, seed).  All of range(n) when k >= n."""
+    import numpy as np
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    i = np.arange(k, dtype=np.int64)
+    lo, hi = i * n // k, (i + 1) * n // k
+    return lo + np.random.default_rng(seed).integers(0, 1 << 62, k) % (hi - lo)
+
+
+def dump_outputs(d: str, torch, seed: int, fields, groups, rows, row_bytes: int) -> dict:
+    """--dump-outputs: what the last timed step left on the device, as DIR/<name>.npy.
+    `groups` = [(windows, {field: tensor})] in window order (one entry per statistics launch),
+    `rows` = the packed-row tensors in position order (uint8, whole rows).  Every window field
+    the step writes becomes <field>.npy (float64, one row per window; the int32 fields convert
+    exactly); when all windows would pass DUMP_WINDOWS_BYTES, a seeded sample of them is kept
+    and window_index.npy names it.  rows.npy holds the row bytes (float32, one row per
+    position) of a seeded sample of positions, rows_index.npy the positions' indices in the
+    rank's row order.  The same arguments give the same sample."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    written = {}
+
+    def save(name, a):
+        np.save(os.path.join(d, name + ".npy"), a)
+        written[name] = int(a.nbytes)
+
+    def pick(parts, idx, width):
+        """rows idx (ascending, over the concatenation) of parts = [(count, tensor viewed (count, width))]"""
+        got, off = [], 0
+        for cnt, t in parts:
+            a, b = np.searchsorted(idx, off), np.searchsorted(idx, off + cnt)
+            if b > a:
+                sel = torch.from_numpy(idx[a:b] - off).to(t.device)
+                got.append(t.view(cnt, width)[sel].cpu().numpy())
+            off += cnt
+        return np.concatenate(got) if got else np.zeros((0, width))
+
+    n_win = sum(nw for nw, _ in groups)
+    if n_win:
+        per = {f: groups[0][1][f].numel() // groups[0][0] for f in fields}
+        widx = spread_sample(n_win, max(1, DUMP_WINDOWS_BYTES // (8 * sum(per.values()))), seed ^ 0xD0D0)
+        save("window_index", widx.astype(np.float64))
+        for f in fields:
+            save(f, pick([(nw, t[f]) for nw, t in groups], widx, per[f]).astype(np.float64))
+    n_pos = sum(r.numel() // row_bytes for r in rows)
+    ridx = spread_sample(n_pos, max(1, DUMP_ROWS_BYTES // (4 * row_bytes)), seed ^ 0x0D0D)
+    save("rows_index", ridx.astype(np.float64))
+    save("rows", pick([(r.numel() // row_bytes, r) for r in rows], ridx, row_bytes).astype(np.float32))
+    return {"dir": d, "bytes": sum(written.values()), "arrays": sorted(written), "windows": int(len(widx)) if n_win else 0,
+            "of_windows": n_win, "row_positions": int(len(ridx)), "of_positions": n_pos}
+
+
 def max_over_ranks(dist, x: float) -> float:
     """The slowest rank's time (gloo, on the host)."""
     if not dist:
@@ -730,7 +804,8 @@ def bench_genome(args, torch, dist, world, rank, binfo):
         gp.run()
     gp.synchronize()
     gp.key_total.zero_()
-    ctx.check(ctx.lib.pbg_set_kernel_timing(ctx.h, 1), "pbg_set_kernel_timing")
+    if args.full:   # library HIP events around the scan kernel and the call stage (the roofline's)
+        ctx.check(ctx.lib.pbg_set_kernel_timing(ctx.h, 1), "pbg_set_kernel_timing")
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -742,16 +817,47 @@ def bench_genome(args, torch, dist, world, rank, binfo):
     if dist:
         dist.barrier()
     elapsed = max_over_ranks(dist, time.perf_counter() - t0)
+    my_sites = gp.n_sites
+    total_sites = sum(lengths)
+    chunks = len(gp.chunks)
+    base = None
+    if rank == 0:
+        base = {
+            "metric": METRIC, "value": round(total_sites * args.steps / elapsed / 1e6, 3), "unit": "Msites/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic (counter-based pileup generated on device chunk by chunk, inside the timed region)",
+            "config": {"workload": (f"configs[3]: synthetic whole genome {args.contigs} contigs x "
+                                    f"{args.contig_len / 1e6:g} Mbp x {n} samples, consensus call + nucdiv + sfs + "
+                                    f"ld(ZnS) + diverge, {args.window / 1e3:g} kb windows, sharded by contig")
+                       if args.config == 3 else
+                       (f"configs[4]: synthetic deep panel {args.contig_len / 1e6:g} Msites x {n} samples, consensus "
+                        f"call + nucdiv + sfs + haplo EHHS, {args.window / 1e3:g} kb windows every {args.step} bp "
+                        f"(overlapping), window blocks per rank with a {args.window - args.step} bp halo"),
+                       "genome_sites": total_sites, "sites_rank0": my_sites, "samples": n, "mean_depth": args.depth,
+                       "window": args.window, "windows_rank0": gp.n_windows, "chunk_sites": args.chunk,
+                       "chunks_rank0": chunks, "parallelism": f"dp{world} (contig-first shards, no collective)"},
+            "pass_mode": "overlapped (two streams)" if args.overlap else "serial (generate, then call, per chunk)",
+        }
+        if args.dump_outputs:
+            base["dump"] = dump_outputs(args.dump_outputs, torch, args.seed, workload.HotPath.fields_for(gp.stats),
+                                        [(g[3], g[4].t) for g in gp.gstats],
+                                        [gp.segment_rows(si) for si in range(len(gp.segments))], ctx.row_bytes)
+    if not args.full:
+        if rank == 0:
+            base["src_sha"] = source_hash()
+            base["build"] = binfo
+            print(json.dumps(base), flush=True)
+        ctx.close()
+        return
     kt, kn = C.c_double(0.0), C.c_uint32(0)
     ctx.check(ctx.lib.pbg_kernel_time(ctx.h, C.byref(kt), C.byref(kn)), "pbg_kernel_time")
     ct, cn = C.c_double(0.0), C.c_uint32(0)
     ctx.check(ctx.lib.pbg_call_time(ctx.h, C.byref(ct), C.byref(cn)), "pbg_call_time")
     ctx.check(ctx.lib.pbg_set_kernel_timing(ctx.h, 0), "pbg_set_kernel_timing")
-    my_sites = gp.n_sites
-    total_sites = sum(lengths)
     sb = gp.survey_bytes(args.steps)
     scan_ms = kt.value / max(1, kn.value)             # per chunk launch, beside the generator
-    chunks = len(gp.chunks)
     achieved_pass = sb / chunks / (scan_ms * 1e-3) / 1e9 if chunks else 0.0
     call_ms_pass = ct.value / max(1, args.steps)
     # the same kernel on one resident chunk with nothing else on the GPU (untimed for `value`):
@@ -790,22 +896,8 @@ def bench_genome(args, torch, dist, world, rank, binfo):
     bpl = sb // max(1, chunks)
     out = None
     if rank == 0:
-        value = total_sites * args.steps / elapsed / 1e6
         out = {
-            "metric": METRIC, "value": round(value, 3), "unit": "Msites/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic (counter-based pileup generated on device chunk by chunk, inside the timed region)",
-            "config": {"workload": (f"configs[3]: synthetic whole genome {args.contigs} contigs x "
-                                    f"{args.contig_len / 1e6:g} Mbp x {n} samples, consensus call + nucdiv + sfs + "
-                                    f"ld(ZnS) + diverge, {args.window / 1e3:g} kb windows, sharded by contig")
-                       if args.config == 3 else
-                       (f"configs[4]: synthetic deep panel {args.contig_len / 1e6:g} Msites x {n} samples, consensus "
-                        f"call + nucdiv + sfs + haplo EHHS, {args.window / 1e3:g} kb windows every {args.step} bp "
-                        f"(overlapping), window blocks per rank with a {args.window - args.step} bp halo"),
-                       "genome_sites": total_sites, "sites_rank0": my_sites, "samples": n, "mean_depth": args.depth,
-                       "window": args.window, "windows_rank0": gp.n_windows, "chunk_sites": args.chunk,
-                       "chunks_rank0": chunks, "parallelism": f"dp{world} (contig-first shards, no collective)"},
+            **base,
             "roofline": {"bound": "hbm", "kernel": "call_scan_kernel", "achieved": round(achieved_pass, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved_pass / HBM_PEAK_GBS, 4),
                          "traffic": traffic, "bytes_per_launch": bpl, "ms_per_launch": round(scan_ms, 4),
@@ -833,7 +925,6 @@ def bench_genome(args, torch, dist, world, rank, binfo):
                                              "events on the call stream)"} if win_ms else None),
             "note": "value includes the on-device generation of every pileup chunk (the input does not fit "
                     "HBM: ~1.8 TB of keys); call_stage is the call kernels alone (library HIP events)",
-            "pass_mode": "overlapped (two streams)" if args.overlap else "serial (generate, then call, per chunk)",
         }
         out["cpu_baseline"] = cpu_baseline(args) if (world == 1 and args.cpu_sample > 0) else None
         if out["cpu_baseline"]:
@@ -1021,7 +1112,8 @@ def main():
 
     # HIP events around the dominant kernel (call_scan_kernel), recorded by the library on the
     # stream it launches on (torch's events only bracket whole stages)
-    ctx.check(ctx.lib.pbg_set_kernel_timing(ctx.h, 1), "pbg_set_kernel_timing")
+    if args.full:
+        ctx.check(ctx.lib.pbg_set_kernel_timing(ctx.h, 1), "pbg_set_kernel_timing")
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -1032,6 +1124,36 @@ def main():
     if dist:
         dist.barrier()
     elapsed = max_over_ranks(dist, time.perf_counter() - t0)
+    total_sites = args.sites * world * args.steps
+    value = total_sites / elapsed / 1e6
+    base = None
+    if rank == 0:
+        base = {
+            "metric": METRIC, "value": round(value, 3), "unit": "Msites/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic (counter-based pileup resident in HBM, generated on device)",
+            "config": {"workload": (("configs[2]: " if (args.sites, n, args.window) == (50_000_000, 12, 10_000)
+                                     else "off-metric shape: ") +
+                                    f"synthetic 1 contig x {args.sites / 1e6:g} Msites x {n} samples per GPU, "
+                                    f"consensus call + nucdiv + sfs + ld(ZnS), {args.window / 1e3:g} kb windows"),
+                       "sites_per_gpu": args.sites, "samples": n, "mean_depth": args.depth,
+                       "window": args.window, "windows_per_gpu": len(wins), "keys_per_gpu": syn.n_keys,
+                       "parallelism": f"dp{world} (independent window-range shards, no collective)",
+                       "pieces": len(pts) - 1},
+        }
+        if args.dump_outputs:
+            base["dump"] = dump_outputs(args.dump_outputs, torch, args.seed, hp.fields_for(stats),
+                                        [(len(wins), hp.out.t)] if wins else [], [hp.rows], ctx.row_bytes)
+    if not args.full:
+        if rank == 0:
+            base["src_sha"] = source_hash()
+            base["build"] = binfo
+            print(json.dumps(base), flush=True)
+        ctx.close()
+        if dist:
+            dist.destroy_process_group()
+        return
     kt, kn = C.c_double(0.0), C.c_uint32(0)
     ctx.check(ctx.lib.pbg_kernel_time(ctx.h, C.byref(kt), C.byref(kn)), "pbg_kernel_time")
     ct, cn = C.c_double(0.0), C.c_uint32(0)
@@ -1052,8 +1174,6 @@ def main():
     call_ms = sum(a.elapsed_time(b) for a, b, _ in ev) / len(ev)
     stats_ms = sum(b.elapsed_time(c) for _, b, c in ev) / len(ev)
     scan_ms = kt.value / max(1, kn.value)            # per call_scan_kernel launch (one per piece)
-    total_sites = args.sites * world * args.steps
-    value = total_sites / elapsed / 1e6
     call_lib_ms = ct.value / max(1, args.steps)      # whole call stage per step (all pieces)
     call_bytes = syn.survey_bytes()          # sum(2k + 5) + 1 + row_bytes per position
     scan_bytes = call_bytes
@@ -1070,18 +1190,7 @@ def main():
     out = None
     if rank == 0:
         out = {
-            "metric": METRIC, "value": round(value, 3), "unit": "Msites/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic (counter-based pileup resident in HBM, generated on device)",
-            "config": {"workload": (("configs[2]: " if (args.sites, n, args.window) == (50_000_000, 12, 10_000)
-                                     else "off-metric shape: ") +
-                                    f"synthetic 1 contig x {args.sites / 1e6:g} Msites x {n} samples per GPU, "
-                                    f"consensus call + nucdiv + sfs + ld(ZnS), {args.window / 1e3:g} kb windows"),
-                       "sites_per_gpu": args.sites, "samples": n, "mean_depth": args.depth,
-                       "window": args.window, "windows_per_gpu": len(wins), "keys_per_gpu": syn.n_keys,
-                       "parallelism": f"dp{world} (independent window-range shards, no collective)",
-                       "pieces": len(pts) - 1},
+            **base,
             "roofline": {"bound": "hbm", "kernel": "call_scan_kernel", "achieved": round(achieved, 2),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic, "bytes_per_launch": scan_bytes_launch, "ms_per_launch": round(scan_ms, 4),

@@ -1,6 +1,6 @@
 """Sampled oracle check of a full-size timed run (test infrastructure: the checker).
 
-bench.py calls `check_windows` after its timed region: a few windows of the run are drawn at
+`bench.py --full` calls `check_windows` after its timed region: a few windows of the run are drawn at
 random, their positions regenerated on the CPU (the oracle's copy of the synthetic generator,
 oracle/popbam_oracle.cpp orc_synth_batch), called by the oracle's restatement of call_base ->
 errmod_cal -> gl2cns -> clean_heterozygotes / segbase / qfilter (pop_utils.cpp:66-201, 280-365;

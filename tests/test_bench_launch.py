@@ -78,9 +78,41 @@ def test_variant_build_refused(monkeypatch):
 def test_gpus_2_on_one_gpu():
     """Both ranks of `--gpus 2` on the box's one GPU (LOCAL_RANK mod device count): a real weak-scaled
     configs[2]-shaped run at a small --sites, timed over both ranks, parity-sampled on rank 0."""
-    p = _run(["--gpus", "2", "--sites", "2000000", "--steps", "3", "--warmup", "1", "--cpu-sample", "0",
+    p = _run(["--gpus", "2", "--sites", "2000000", "--steps", "3", "--warmup", "1", "--full", "--cpu-sample", "0",
               "--parity-windows", "4"], timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["build"]["kind"] == "product"
     assert d["parity_sampled"] and d["rows_crosscheck"]["identical"]
+
+
+FULL_ONLY = ("roofline", "call_stage", "window_stats", "pcie_inclusive", "end_to_end", "cli", "cpu_baseline",
+             "parity_sampled", "parity_sample", "rows_crosscheck")
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline figure only (--steps timed steps, ms_per_step,
+    value = positions / step time) and none of the --full legs; --dump-outputs writes the last
+    step's window outputs and sampled rows as float32 / float64 .npy files."""
+    import numpy as np
+    sites, out = 300_000, tmp_path / "dump"
+    p = _run(["--gpus", "1", "--sites", str(sites), "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _line(p)
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["build"]["kind"] == "product"
+    assert d["unit"] == "Msites/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["ms_per_step"] > 0
+    # value and ms_per_step are the same measurement; both are rounded in the line (ms to 1e-4)
+    assert d["value"] == pytest.approx(sites / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-4 / d["ms_per_step"] + 1e-6)
+    assert not [k for k in FULL_ONLY if k in d]
+    files = sorted(f for f in os.listdir(out))
+    assert files == sorted(a + ".npy" for a in d["dump"]["arrays"])
+    arrs = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    nw = (sites - 1) // 10_000
+    assert arrs["num_sites"].shape == (nw, 1) and arrs["pi"].shape == (nw, 2) and arrs["ld_val"].shape == (nw, 2)
+    assert np.array_equal(arrs["window_index"], np.arange(nw))
+    assert arrs["rows"].shape == (sites, 2) and np.array_equal(arrs["rows_index"], np.arange(sites))
+    assert arrs["num_sites"].max() > 0 and arrs["segsites"].max() > 0 and arrs["rows"].max() > 0

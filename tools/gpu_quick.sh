@@ -11,8 +11,10 @@ if [ -n "${TESTS:-}" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 300 python bench.py --cpu-sample 0 ${BENCH_ARGS:-} > gpurun_out/bench_q.json 2> gpurun_out/bench_q.err || exit $?
-  cat gpurun_out/bench_q.json
+  # the --full line (roofline, stage breakdown, parity; no CPU baselines), under $OUT (default bench_out)
+  O=${OUT:-bench_out}; mkdir -p "$O"
+  timeout -k 10 300 python bench.py --full --cpu-sample 0 ${BENCH_ARGS:-} > "$O/bench_q.json" 2> "$O/bench_q.err" || exit $?
+  cat "$O/bench_q.json"
 fi
 if [ "${PROF:-1}" = "1" ]; then
   rm -rf gpurun_out/prof_q
