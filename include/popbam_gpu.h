@@ -189,6 +189,30 @@ int pbg_window_stats(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_
                      uint32_t n_win, const pbg_stat_opts *opts, const pbg_window_out *out,
                      void *stream);
 
+/* LD decay (an extension; the reference stops at ZnS, one number per window and population):
+ * r^2 against the distance between sites.  For window [beg, end) and population i, the variable
+ * sites v_0 < v_1 < ... are the window's segregating rows whose derived count m in the population
+ * has min_freq <= m <= n_i - min_freq (calc_zns's test, pop_ld.cpp:201-252).  Every pair a < b
+ * has distance d = v_b - v_a >= 1 and bin k = (d - 1) / bin_bp, so bin k holds distances
+ * k*bin_bp + 1 .. (k + 1)*bin_bp; pairs with k >= n_bins are dropped.  pairs[k] counts bin k's
+ * pairs; r2_sum[k] is the sequential double sum, from +0.0 in pair order (a ascending, then b
+ * ascending), of the r^2 table entries ZnS adds -- bit for bit what a calc_zns-style double loop
+ * with bin[k] += r2 gives, the same on every run; n_var is the number of variable sites (not the
+ * reference's num_snps).  Windows with beg >= end and populations without variable sites give
+ * zeros.  Asynchronous like pbg_window_stats, and free to interleave with it on one stream;
+ * lists of more than 1024 variable sites take a slice of the statistics workspace (exhaustion:
+ * pbg_check, PBG_E_RANGE).  PBG_E_ARG for bin_bp < 1, n_bins outside 1..PBG_DECAY_MAX_BINS,
+ * min_freq not 1 or 2, or a null argument. */
+#define PBG_DECAY_MAX_BINS 256
+typedef struct { int32_t bin_bp, n_bins, min_freq, _pad; } pbg_decay_opts;
+typedef struct {            /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int64_t *pairs;         /* [n_win*n_pops*n_bins] */
+    double  *r2_sum;        /* [n_win*n_pops*n_bins] */
+    int32_t *n_var;         /* [n_win*n_pops]        */
+} pbg_decay_out;
+int pbg_window_ld_decay(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                        uint32_t n_win, const pbg_decay_opts *opts, const pbg_decay_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -225,6 +249,11 @@ typedef struct {
                               first window): 0 = this call's window count; > 0 = print it with
                               this total (a block of a longer run that starts the run);
                               < 0 = no header (a later block of a longer run)                */
+    int32_t  decay_bin, decay_bins;   /* ld -o 0 --decay=BIN,NBINS (0 = off): a streamed run also
+                              bins r^2 by distance (pbg_window_ld_decay on the command's windows) and
+                              appends, per population, "decay[pop]:" the bins' mean r^2 (NA for an
+                              empty bin) and "pairs[pop]:" their pair counts, comma-separated, after
+                              the reference's columns; they ignore min_snps                      */
 } pbg_cmd;
 
 /* Runs `popbam <cmd>` over a HOST pileup batch that covers contig positions
@@ -239,7 +268,8 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
 
 /* print_<stat> for windows whose results were copied to the HOST: `host_out` holds host
  * arrays laid out as pbg_window_out, `wbeg`/`wend` the contig coordinates the reference
- * prints (+1 applied here).  Same return convention as pbg_run.                          */
+ * prints (+1 applied here).  Same return convention as pbg_run.  It takes no decay arrays and
+ * prints the reference's columns only, whatever the command's decay_bin says.              */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

@@ -29,7 +29,9 @@ EXPORTS = ["pbg_create", "pbg_destroy", "pbg_last_error", "pbg_row_bytes", "pbg_
            "pbg_device_count", "pbg_call_sites", "pbg_window_stats", "pbg_check", "pbg_run", "pbg_take_text",
            "pbg_format", "pbg_build_info", "pbg_set_kernel_timing", "pbg_kernel_time", "pbg_call_time", "pbg_synth_max_keys",
            "pbg_synth_pileup", "pbg_stream_open", "pbg_stream_push", "pbg_stream_push_compact", "pbg_stream_finish", "pbg_stream_text",
-           "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close"]
+           "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay"]
+
+PBG_DECAY_MAX_BINS = 256
 
 
 class PbgParams(C.Structure):
@@ -77,7 +79,15 @@ class PbgCmd(C.Structure):
                 ("min_freq", C.c_int32), ("outidx", C.c_int32), ("jc", C.c_int32), ("windowed", C.c_int32),
                 ("win_size", C.c_int64), ("beg", C.c_int32), ("end", C.c_int32), ("chr_name", C.c_char_p),
                 ("sample_names", C.POINTER(C.c_char_p)), ("pop_names", C.POINTER(C.c_char_p)),
-                ("refid", C.c_char_p), ("ms_windows", C.c_int32)]
+                ("refid", C.c_char_p), ("ms_windows", C.c_int32), ("decay_bin", C.c_int32), ("decay_bins", C.c_int32)]
+
+
+class PbgDecayOpts(C.Structure):
+    _fields_ = [("bin_bp", C.c_int32), ("n_bins", C.c_int32), ("min_freq", C.c_int32), ("_pad", C.c_int32)]
+
+
+class PbgDecayOut(C.Structure):
+    _fields_ = [("pairs", C.c_void_p), ("r2_sum", C.c_void_p), ("n_var", C.c_void_p)]
 
 
 class PbgStreamProf(C.Structure):
@@ -131,6 +141,8 @@ def load(torch_first: bool = True):
     lib.pbg_call_sites.restype = C.c_int
     lib.pbg_window_stats.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgStatOpts), P(PbgWindowOut), vp]
     lib.pbg_window_stats.restype = C.c_int
+    lib.pbg_window_ld_decay.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgDecayOpts), P(PbgDecayOut), vp]
+    lib.pbg_window_ld_decay.restype = C.c_int
     lib.pbg_build_info.argtypes = []
     lib.pbg_build_info.restype = C.c_char_p
     lib.pbg_check.argtypes = [vp, vp]

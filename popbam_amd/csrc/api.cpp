@@ -71,7 +71,7 @@ hipError_t upload(T **dst, const std::vector<T> &v) {
 }  // namespace
 
 namespace pbg {
-extern const int kBuildKind_call, kBuildKind_stats;
+extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay;
 }
 
 namespace {
@@ -318,7 +318,7 @@ void pbg_destroy(pbg_ctx *c) {
                     (void *)c->d_fbeta, (void *)c->d_lb, (void *)c->d_oe, c->d_scantab, (void *)c->d_err, (void *)c->d_ws, (void *)c->d_wsoff, (void *)c->d_zns,
                     (void *)c->deep.sites, (void *)c->deep.tasks, (void *)c->deep.info, (void *)c->deep.count,
                     (void *)c->deep.blk_cnt, (void *)c->deep.raw, (void *)c->deep.pend,
-                    (void *)c->d_segcnt, (void *)c->d_synth})
+                    (void *)c->d_segcnt, (void *)c->d_synth, (void *)c->d_decay_used})
         if (p) (void)hipFree(p);
     for (auto &t : c->tmpl) (void)hipFree(t.second);
     for (auto *v : {&c->ev, &c->evc})
@@ -448,7 +448,7 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 }
 
 const char *pbg_build_info(void) {
-    const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats});
+    const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -626,6 +626,72 @@ int pbg_window_stats(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
     A.lds = pbg::stats_lds_layout(n, np, c->dp.sfs_stride, o->stats, 0, (int)mw, segcap);
     if (A.lds.bytes > 64 * 1024) return fail(c, PBG_E_ARG, "statistics need more LDS than a workgroup has");
     HIPCHK(c, pbg::launch_window_stats(c->row_bytes, c->dp, c->dt, rows, n_rows, n_win, A, (hipStream_t)stream, c->n_cu));
+    return PBG_OK;
+}
+
+int pbg_window_ld_decay(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                        const pbg_decay_opts *o, const pbg_decay_out *out, void *stream) {
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    if (o->bin_bp < 1) return fail(c, PBG_E_ARG, "decay: bin_bp must be at least 1");
+    if (o->n_bins < 1 || o->n_bins > PBG_DECAY_MAX_BINS) return fail(c, PBG_E_ARG, "decay: n_bins must be in [1, 256]");
+    if (o->min_freq != 1 && o->min_freq != 2) return fail(c, PBG_E_ARG, "decay: min_freq must be 1 or 2");
+    if (n_win == 0) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    const int np = c->dp.npops;
+    if ((uint64_t)n_win * (uint64_t)np > 0x7FFFFFFFull) return fail(c, PBG_E_ARG, "decay: too many windows");
+    HIPCHK(c, hipSetDevice(c->device));
+    pbg::DecayArgs A{};
+    A.pool_div = 1;
+#ifdef PBG_BOUNDS
+    if (const char *st = std::getenv("PBG_BOUNDS_SELFTEST"))
+        if (std::string(st) == "pool") A.pool_div = 2;   // positive control of the pool store checks
+#endif
+    A.wins = wins;
+    A.bin_bp = o->bin_bp;
+    A.n_bins = o->n_bins;
+    A.min_freq = o->min_freq;
+    const size_t lds = pbg::decay_lds_bytes(c->row_bytes, c->dp, A);
+    // The workspace is pbg_window_stats's pool: it only ever grows, so that call's cached plans stay
+    // valid; the pool is scratch within a call, and calls on one stream run in order.  Sized from the
+    // window list (every window longer than the LDS list capacity, all rows variable); validated
+    // lists are cached per device pointer like the statistics plans.
+    bool known = false;
+    for (const auto &pl : c->decay_plans)
+        if (pl.wins == (const void *)wins && pl.n_win == n_win && pl.n_rows == n_rows) known = true;
+    if (!known) {
+        std::vector<pbg_window> hw(n_win);
+        HIPCHK(c, hipMemcpyAsync(hw.data(), wins, n_win * sizeof(pbg_window), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+        const uint64_t mw = c->row_bytes == 16 ? 2 : 1;
+        uint64_t worst = 0;
+        for (uint32_t i = 0; i < n_win; ++i) {
+            if (hw[i].beg < 0 || (hw[i].end > hw[i].beg && (uint32_t)hw[i].end > n_rows))
+                return fail(c, PBG_E_RANGE, "window outside the row range");
+            const uint64_t len = hw[i].end > hw[i].beg ? (uint64_t)(hw[i].end - hw[i].beg) : 0;
+            if (len > (uint64_t)pbg::kDecayCap) worst += (uint64_t)np * (A.compact ? len : mw * len + (len + 1) / 2);
+        }
+        constexpr uint64_t kPoolMax = 512ull << 20;   // words (4 GiB), as pbg_window_stats
+        const uint64_t want = std::max<uint64_t>(1024, std::min(worst, kPoolMax));
+        if (want * 8 > c->ws_cap) {
+            if (c->d_ws) HIPCHK(c, hipFree(c->d_ws));
+            c->d_ws = nullptr;
+            c->ws_cap = 0;
+            HIPCHK(c, hipMalloc(&c->d_ws, want * 8));
+            c->ws_cap = want * 8;
+        }
+        if (c->decay_plans.size() >= 16) c->decay_plans.erase(c->decay_plans.begin());
+        c->decay_plans.push_back({wins, n_win, n_rows});
+    }
+    if (!c->d_decay_used) HIPCHK(c, hipMalloc((void **)&c->d_decay_used, 8));
+    A.pool = c->d_ws;
+    A.pool_cap = c->ws_cap / 8;
+    A.pool_used = c->d_decay_used;
+    A.err = c->d_err;
+    A.pairs = out->pairs;
+    A.r2_sum = out->r2_sum;
+    A.n_var = out->n_var;
+    HIPCHK(c, hipMemsetAsync(A.pool_used, 0, 8, (hipStream_t)stream));
+    HIPCHK(c, pbg::launch_window_decay(c->row_bytes, c->dp, c->dt, rows, n_rows, n_win, A, lds, (hipStream_t)stream));
     return PBG_OK;
 }
 

@@ -297,6 +297,24 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                     if (sok) o.f(w.ld_val[i]); else o.na();
                 }
             }
+            // --decay: per population the bins' mean r^2 and pair counts, appended after the
+            // reference's columns (the default output is unchanged); not subject to -n
+            if (c.output == 0 && c.decay_bin > 0 && c.decay_bins > 0 &&
+                w.decay_pairs.size() == (size_t)np * c.decay_bins && w.decay_sum.size() == w.decay_pairs.size())
+                for (int i = 0; i < np; i++) {
+                    const size_t b0 = (size_t)i * c.decay_bins;
+                    o.t("\tdecay[" + pn(c, i) + "]:\t");
+                    for (int k = 0; k < c.decay_bins; k++) {
+                        if (k) o.t(",");
+                        if (w.decay_pairs[b0 + k] == 0) o.t("NA");
+                        else o.f(w.decay_sum[b0 + k] / (double)w.decay_pairs[b0 + k]);
+                    }
+                    o.t("\tpairs[" + pn(c, i) + "]:\t");
+                    for (int k = 0; k < c.decay_bins; k++) {
+                        if (k) o.t(",");
+                        o.i(w.decay_pairs[b0 + k]);
+                    }
+                }
             break;
         case PBG_CMD_DIVERGE:  // print_diverge pop_diverge.cpp:496-574
             if (c.output == 0) {

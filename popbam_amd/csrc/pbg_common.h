@@ -313,6 +313,27 @@ struct StatsArgs {
 };
 #define PBG_POOL_OK(A, idx, lo, len) PBG_STORE_OK((A).err, (idx) - (lo), (len) / (A).pool_div, len, ::pbg::kErrPool)
 
+// window_decay_kernel (pbg_window_ld_decay): binned r^2 against distance per (window, population)
+constexpr int kDecayCap = 1024;      // variable sites of a chain kept in LDS (beyond: workspace)
+constexpr int kDecayR2Lds = 4096;    // a population's r^2 table is copied to LDS up to this many doubles
+struct DecayArgs {
+    const pbg_window *wins;
+    int32_t bin_bp, n_bins, min_freq;
+    int32_t compact;      // lists hold the population-compacted mask | popcount << 26 (every population <= 26
+                          // samples, one-word masks); else the raw masks
+    uint32_t tab_bytes;   // dynamic LDS: [r^2 table of the chain's population: tab_bytes][the list]
+    // lists longer than kDecayCap take a slice of the statistics workspace with one atomic add; an
+    // exhausted pool sets err bit 4 (pbg_check -> PBG_E_RANGE) and the chain's outputs are zero
+    uint64_t *pool;
+    uint64_t pool_cap;                    // u64 words
+    unsigned long long *pool_used;        // [1] words taken, zeroed per call
+    int *err;
+    int64_t *pairs;                       // [n_win*npops*n_bins] or null
+    double *r2_sum;                       // [n_win*npops*n_bins] or null
+    int32_t *n_var;                       // [n_win*npops] or null
+    uint32_t pool_div;                    // PBG_BOUNDS store checks, as StatsArgs::pool_div
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -445,5 +466,9 @@ hipError_t launch_synth_tmpl(uint64_t seed, uint16_t *tmpl, hipStream_t stream);
 size_t synth_scratch_words(uint32_t n_sites);
 hipError_t launch_window_stats(int row_bytes, const DevParams &P, const DevTables &T, const void *rows,
                                uint32_t n_rows, uint32_t n_win, const StatsArgs &A, hipStream_t stream, int n_cu);
+// decay_kernel.hip; decay_lds_bytes: the dynamic LDS a launch needs (sets A.tab_bytes)
+size_t decay_lds_bytes(int row_bytes, const DevParams &P, DecayArgs &A);
+hipError_t launch_window_decay(int row_bytes, const DevParams &P, const DevTables &T, const void *rows,
+                               uint32_t n_rows, uint32_t n_win, const DecayArgs &A, size_t lds, hipStream_t stream);
 
 }  // namespace pbg

@@ -46,7 +46,9 @@ struct StreamBufs {
     size_t cb_cap = 0;
     void *d_out = nullptr;               // window outputs of one command
     size_t out_cap = 0;
-    std::vector<WinList> wins;           // most recent last
+    void *d_decay = nullptr;             // ld --decay: pairs | r2_sum of one command
+    size_t decay_cap = 0;
+    std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };
 
@@ -86,6 +88,15 @@ struct pbg_ctx {
     size_t zns_cap = 0;   // bytes of d_zns
     size_t ws_cap = 0, wsoff_cap = 0, segcnt_cap = 0;
     int32_t *d_segcnt = nullptr;
+    // pbg_window_ld_decay: window lists already validated (their workspace need is met by ws_cap,
+    // which only grows), kept apart from `plans` so neither call disturbs the other's cache; and
+    // the call's own pool counter (pbg_window_stats keeps its counter in d_wsoff)
+    struct DecayPlan {
+        const void *wins;
+        uint32_t n_win, n_rows;
+    };
+    std::vector<DecayPlan> decay_plans;
+    unsigned long long *d_decay_used = nullptr;
     // samples deeper than the register sort width (call kernel): queues + parked info bytes
     pbg::DeepBufs deep{};
     size_t deep_sites_cap = 0, deep_info_cap = 0;

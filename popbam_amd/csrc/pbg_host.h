@@ -32,6 +32,10 @@ struct WindowHost {
     std::vector<int32_t> seg_pop;
     std::vector<double> theta_w;
     std::vector<std::vector<int32_t>> sfs_bins;
+    // ld -o 0 --decay (pbg_cmd.decay_bin > 0): pairs and r^2 sum of bin k of population p at
+    // [p * decay_bins + k] (pbg_window_ld_decay); empty when the caller has none (pbg_format)
+    std::vector<int64_t> decay_pairs;
+    std::vector<double> decay_sum;
 };
 
 // print_nucdiv / print_sfs / print_ld / print_diverge / print_haplo (TSV, byte-identical)

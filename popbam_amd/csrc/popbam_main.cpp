@@ -98,6 +98,7 @@ struct Options {
     int min_depth = 3, max_depth = 255, min_rmsQ = 25, min_snpQ = 25;   // popbam.cpp:79-93
     unsigned char min_mapQ = 13, min_baseQ = 13;
     int min_sites = 10, output = 0, min_snps = 10, min_freq = 1;          // <cmd>Data constructors
+    int decay_bin = 0, decay_bins = 0;                                    // ld --decay=BIN,NBINS (0: off)
     unsigned int win_size = 0;
     long double het_prior = 0.0001L;                                      // -z: parsed, unused
 };
@@ -289,6 +290,23 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
     if ((cmd == "ld" || cmd == "haplo" || cmd == "snp") && (o.output < 0 || o.output > 2))
         throw Fatal{"Not a valid output option"};
     if (cmd == "diverge" && (o.output < 0 || o.output > 1)) throw Fatal{"Not a valid output option"};
+    if (cmd == "ld")   // extension: --decay=BIN,NBINS (one long token: never <in.bam> or <region>)
+        for (const std::string &a : argv) {
+            if (a != "--decay" && a.compare(0, 8, "--decay=") != 0) continue;
+            // BIN in 1..2^31-1 and NBINS in 1..PBG_DECAY_MAX_BINS, decimal digits only
+            const std::string v = a.size() > 8 ? a.substr(8) : "";
+            const size_t comma = v.find(',');
+            const std::string sb = v.substr(0, comma), sn = comma == std::string::npos ? "" : v.substr(comma + 1);
+            auto digits = [](const std::string &s) {
+                return !s.empty() && s.size() <= 10 && s.find_first_not_of("0123456789") == std::string::npos;
+            };
+            if (!digits(sb) || !digits(sn)) throw Fatal{"Not a valid decay option"};
+            const long long bin = std::stoll(sb), nb = std::stoll(sn);
+            if (bin < 1 || bin > 2147483647LL || nb < 1 || nb > PBG_DECAY_MAX_BINS) throw Fatal{"Not a valid decay option"};
+            if (o.output != 0) throw Fatal{"--decay needs -o 0"};
+            o.decay_bin = (int)bin;
+            o.decay_bins = (int)nb;
+        }
     const std::vector<std::string> g = tk.globals();
     if (g.size() < 2) throw Fatal{"Need to specify BAM file name"};
     o.bamfile = g[0];
@@ -740,6 +758,8 @@ std::string run(const std::string &cmd, const std::vector<std::string> &argv, in
         c.pop_names = pn.data();
         c.refid = refid.c_str();
         c.ms_windows = (blocks.size() > 1 || world > 1) ? (int32_t)(bi == 0 ? ms0 : -1) : 0;
+        c.decay_bin = o.decay_bin;
+        c.decay_bins = o.decay_bins;
         t0 = Clock::now();
         pbf_kstream *ks = nullptr;
         if (pbf_kstream_open(o.bamfile.c_str(), std::max(1, threads), piece, tid, (int32_t)lo, (int32_t)hi,

@@ -21,6 +21,7 @@
 //   haplo    calc_nhaps / calc_ehhs / calc_minDxy    pop_haplo.cpp:208-363
 //   tree     calc_diff_matrix      pop_tree.cpp:472-494
 #include "pbg_common.h"
+#include "pbg_rows.h"
 
 namespace pbg {
 extern const int kBuildKind_stats = PBG_BUILD_KIND;   // pbg_build_info()
@@ -30,54 +31,14 @@ namespace pbg {
 
 namespace {
 
-__device__ __forceinline__ unsigned pc(uint64_t x) { return (unsigned)__popcll(x); }
-
-// The sample bits of a row: one u64 for 2 / 4 / 8-byte rows, two for 16-byte rows (n <= 126;
-// the reference's masks are one u64, n <= 64, popbam.cpp:168).  Every statistic below is
-// written once over the mask type M: a bitwise and / complement, equality, the unsigned order
-// (std::list::sort in calc_ehhs), popcount and a bit test.
-struct M2 {
-    uint64_t lo, hi;
-};
-__device__ __forceinline__ M2 operator&(M2 a, M2 b) { return {a.lo & b.lo, a.hi & b.hi}; }
-__device__ __forceinline__ M2 operator~(M2 a) { return {~a.lo, ~a.hi}; }
-__device__ __forceinline__ bool operator==(M2 a, M2 b) { return a.lo == b.lo && a.hi == b.hi; }
-__device__ __forceinline__ bool operator<(M2 a, M2 b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
-__device__ __forceinline__ unsigned pc(M2 x) { return pc(x.lo) + pc(x.hi); }
-__device__ __forceinline__ bool nonzero(uint64_t x) { return x != 0; }
-__device__ __forceinline__ bool nonzero(M2 x) { return (x.lo | x.hi) != 0; }
-__device__ __forceinline__ uint32_t bit(uint64_t x, int v) { return (uint32_t)(x >> v) & 1u; }
-__device__ __forceinline__ uint32_t bit(M2 x, int v) { return (uint32_t)(v < 64 ? x.lo >> v : x.hi >> (v - 64)) & 1u; }
-template <class M>
-__device__ __forceinline__ M pop_mask(const DevParams &P, int i);
-template <>
-__device__ __forceinline__ uint64_t pop_mask<uint64_t>(const DevParams &P, int i) { return P.pop_mask[i]; }
-template <>
-__device__ __forceinline__ M2 pop_mask<M2>(const DevParams &P, int i) { return {P.pop_mask[i], P.pop_mask_hi[i]}; }
 __device__ __forceinline__ uint64_t shfl_xor_mask(uint64_t x, int o) {
     return ((uint64_t)(uint32_t)__shfl_xor((int)(x >> 32), o, 64) << 32) | (uint32_t)__shfl_xor((int)x, o, 64);
 }
 __device__ __forceinline__ M2 shfl_xor_mask(M2 x, int o) { return {shfl_xor_mask(x.lo, o), shfl_xor_mask(x.hi, o)}; }
-template <int RB>
-struct RowMask { using T = uint64_t; };
-template <>
-struct RowMask<16> { using T = M2; };
-
 // x86 SSE produces the "default NaN" (sign bit set) for invalid operations; glibc prints it
 // as "-nan".  Canonicalise device NaNs the same way before they reach the formatter.
 __device__ __forceinline__ double x86nan(double v) { return (v != v) ? __longlong_as_double(0xFFF8000000000000LL) : v; }
 
-// exclusive wave prefix of a lane count (DPP inclusive scan, see call_kernel.hip)
-__device__ __forceinline__ uint32_t wave_incl_scan_s(uint32_t v) {
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
-    return (uint32_t)x;
-}
 __device__ __forceinline__ int wave_sum(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -85,28 +46,6 @@ __device__ __forceinline__ int wave_sum(int v) {
 __device__ __forceinline__ int wave_min(int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
     return v;
-}
-
-// Row r (0 .. 16/RB - 1) of a 16-byte word of RB-byte rows (include/popbam_gpu.h row format).
-template <int RB>
-__device__ __forceinline__ void row_in_word(const uint4 &q, int r, typename RowMask<RB>::T &types, bool &counted,
-                                            bool &seg) {
-    if constexpr (RB == 16) {
-        types.lo = (uint64_t)q.x | ((uint64_t)q.y << 32);
-        types.hi = ((uint64_t)q.z | ((uint64_t)q.w << 32)) & 0x3FFFFFFFFFFFFFFFULL;
-        counted = (q.w >> 30) & 1u;
-        seg = (q.w >> 31) & 1u;
-    } else {
-        const uint32_t wd[4] = {q.x, q.y, q.z, q.w};
-        constexpr int W = RB * 8;
-        uint64_t v;
-        if constexpr (RB == 8) v = (uint64_t)wd[2 * r] | ((uint64_t)wd[2 * r + 1] << 32);
-        else if constexpr (RB == 4) v = wd[r];
-        else v = (wd[r >> 1] >> (16 * (r & 1))) & 0xFFFFu;
-        counted = (v >> (W - 2)) & 1;
-        seg = (v >> (W - 1)) & 1;
-        types = v & ((W == 64) ? 0x3FFFFFFFFFFFFFFFULL : ((1ULL << (W - 2)) - 1));
-    }
 }
 
 }  // namespace
@@ -896,27 +835,9 @@ constexpr int kZnsG = PBG_ZNS_GROUPS;        // 16-lane producer groups per chai
 constexpr int kZnsMaxC = 60 / kZnsG;         // chains per workgroup (64 + 16 G C <= 1024 threads)
 constexpr int kZnsR = 8;                     // rounds per phase
 constexpr int kZnsRingStride = 18;           // doubles per (round, chain): 16 values + 2 pad (LDS banks)
+static_assert(kZnsR % kZnsG == 0 && 64 + 16 * kZnsG * kZnsMaxC <= 1024,
+              "a phase's rounds deal out evenly over the producer groups; the workgroup fits 1024 threads");
 
-// the sample bits of t inside population mask pm, packed to bit positions 0..pc(pm)-1
-__device__ __forceinline__ uint32_t pext32(uint64_t t, uint64_t pm, uint32_t &k) {
-    uint32_t out = 0;
-    while (pm) {
-        const int p = __builtin_ctzll(pm);
-        out |= (uint32_t)((t >> p) & 1u) << k;
-        ++k;
-        pm &= pm - 1;
-    }
-    return out;
-}
-__device__ __forceinline__ uint32_t compact32(uint64_t t, uint64_t pm) {
-    uint32_t k = 0;
-    return pext32(t, pm, k);
-}
-__device__ __forceinline__ uint32_t compact32(M2 t, M2 pm) {
-    uint32_t k = 0;
-    const uint32_t lo = pext32(t.lo, pm.lo, k);
-    return lo | pext32(t.hi, pm.hi, k);
-}
 // row-step rounds of a chain of V sites: sum over the V - 1 rows of ceil(row length / 16)
 __device__ __forceinline__ long long zns_rounds(int V) {
     const long long N = V > 1 ? V - 1 : 0, q = N / 16, r = N % 16;

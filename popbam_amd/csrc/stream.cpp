@@ -367,9 +367,31 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
     HIPCHK(c, d2h(h_d1.data(), d1, n_d1 * 8));
     HIPCHK(c, d2h(h_d2.data(), d2, n_d2 * 8));
     HIPCHK(c, d2h(h_d3.data(), d3, n_d3 * 8));
+    // ld -o 0 --decay: the decay kernel over the same windows (its columns follow the reference's)
+    const bool decay = stats == PBG_S_ZNS && cmd->decay_bin > 0;
+    std::vector<int64_t> h_dpairs;
+    std::vector<double> h_dsum;
+    if (decay) {
+        const size_t szk = szp * (size_t)std::max(cmd->decay_bins, 0);
+        if (c->sb.decay_cap < szk * 16 + 16) {
+            if (c->sb.d_decay) HIPCHK(c, hipFree(c->sb.d_decay));
+            c->sb.d_decay = nullptr;
+            c->sb.decay_cap = 0;
+            HIPCHK(c, hipMalloc(&c->sb.d_decay, szk * 16 + 16));
+            c->sb.decay_cap = szk * 16 + 16;
+        }
+        const pbg_decay_opts dopt{cmd->decay_bin, cmd->decay_bins, cmd->min_freq, 0};
+        const pbg_decay_out dout{(int64_t *)c->sb.d_decay, (double *)c->sb.d_decay + szk, nullptr};
+        if ((rc = pbg_window_ld_decay(c, d_rows, dsites, d_win, nw, &dopt, &dout, s))) return rc;
+        if ((rc = pbg_check(c, s))) return rc;
+        h_dpairs.resize(szk);
+        h_dsum.resize(szk);
+        HIPCHK(c, d2h(h_dpairs.data(), dout.pairs, szk * 8));
+        HIPCHK(c, d2h(h_dsum.data(), dout.r2_sum, szk * 8));
+    }
     HIPCHK(c, hipStreamSynchronize(s));
     pbg::WindowHost wh;
-    auto slice = [](const auto &v, size_t off, size_t cnt) {
+    auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
         return std::vector<T>(v.begin() + off, v.begin() + off + cnt);
     };
@@ -390,7 +412,12 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
                 }
                 break;
             case PBG_S_ZNS: case PBG_S_OMEGA:
-                wh.ld_snps = slice(h_i1, i * np, np); wh.ld_val = slice(h_d1, i * np, np); break;
+                wh.ld_snps = slice(h_i1, i * np, np); wh.ld_val = slice(h_d1, i * np, np);
+                if (decay) {
+                    const size_t per = (size_t)np * cmd->decay_bins;
+                    wh.decay_pairs = slice(h_dpairs, i * per, per); wh.decay_sum = slice(h_dsum, i * per, per);
+                }
+                break;
             case PBG_S_WALL:
                 wh.ld_snps = slice(h_i1, i * np, np); wh.ld_val = slice(h_d1, i * np, np);
                 wh.ld_q = slice(h_d2, i * np, np); break;
@@ -415,7 +442,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out})
+    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay})
         if (p) (void)hipFree(p);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

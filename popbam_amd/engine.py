@@ -76,6 +76,7 @@ class _Cmd:
         self._refid = refid.encode()
         c.refid = self._refid
         c.ms_windows = ms_windows
+        c.decay_bin, c.decay_bins = o.decay_bin, o.decay_bins
         self.c = c
 
 

@@ -30,6 +30,8 @@ BAM_HEADERIN = 0x80
 # popbam_func_t (popbam.h:208)
 CMD_IDS = {"snp": 0, "haplo": 1, "diverge": 2, "tree": 3, "nucdiv": 4, "ld": 5, "sfs": 6}
 
+DECAY_MAX_BINS = 256   # PBG_DECAY_MAX_BINS (include/popbam_gpu.h)
+
 
 class PopbamError(RuntimeError):
     """Mirrors fatal_error (pop_utils.cpp:510-519): message + non-zero exit in the CLI."""
@@ -56,6 +58,8 @@ class Options:
     min_freq: int = 1
     outgroup: str = ""
     dist: str = "pdist"
+    decay_bin: int = 0     # ld --decay=BIN,NBINS: bin width in bases (0: off)
+    decay_bins: int = 0
     errors: list = field(default_factory=list)
 
 
@@ -197,7 +201,18 @@ def parse_args(cmd: str, argv: list[str]) -> Options:
         raise PopbamError("Not a valid output option")
     if cmd == "diverge" and not 0 <= o.output <= 1:
         raise PopbamError("Not a valid output option")
-    glob = [v for t, v in toks if t in ("G", "U", "N")]
+    if cmd == "ld":   # extension: --decay=BIN,NBINS (one long token: never <in.bam> or <region>)
+        for a in argv:
+            if a != "--decay" and not a.startswith("--decay="):
+                continue
+            # BIN in 1..2^31-1 and NBINS in 1..PBG_DECAY_MAX_BINS, decimal digits only
+            m = re.fullmatch(r"([0-9]{1,10}),([0-9]{1,10})", a[8:])
+            if not m or not 1 <= int(m.group(1)) <= 0x7FFFFFFF or not 1 <= int(m.group(2)) <= DECAY_MAX_BINS:
+                raise PopbamError("Not a valid decay option")
+            if o.output != 0:
+                raise PopbamError("--decay needs -o 0")
+            o.decay_bin, o.decay_bins = int(m.group(1)), int(m.group(2))
+    glob =[v for t, v in toks if t in ("G", "U", "N")]
     if len(glob) < 2:
         raise PopbamError("Need to specify BAM file name")
     o.bamfile, o.region = glob[0], glob[1]

@@ -143,6 +143,41 @@ class WindowOutputs:
         return o
 
 
+class LdDecay:
+    """pbg_window_ld_decay: r^2 binned by the distance between variable sites, per window and
+    population.  Owns the three device arrays -- pairs[n_win, n_pops, n_bins] (int64),
+    r2_sum[n_win, n_pops, n_bins] (float64), n_var[n_win, n_pops] (int32) -- and runs on a
+    HotPath's rows and windows, or on any rows tensor with a window list."""
+
+    def __init__(self, ctx: _lib.Context, n_win: int, bin_bp: int, n_bins: int, min_freq: int = 1,
+                 device: str = "cuda"):
+        self.ctx, self.n_win, self.bin_bp, self.n_bins = ctx, n_win, bin_bp, n_bins
+        np_ = ctx.params.n_pops
+        self.opts = _lib.PbgDecayOpts(bin_bp, n_bins, min_freq, 0)
+        self.pairs = torch.zeros((n_win, np_, max(n_bins, 0)), dtype=torch.int64, device=device)
+        self.r2_sum = torch.zeros((n_win, np_, max(n_bins, 0)), dtype=torch.float64, device=device)
+        self.n_var = torch.zeros((n_win, np_), dtype=torch.int32, device=device)
+        self.out = _lib.PbgDecayOut(_ptr(self.pairs), _ptr(self.r2_sum), _ptr(self.n_var))
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_ld_decay(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                                C.byref(self.opts), C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_ld_decay")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", bin_bp: int, n_bins: int, min_freq: int = 1, stream=None) -> "LdDecay":
+        """The decay of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, bin_bp, n_bins, min_freq, str(hp.rows.device))(
+            hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 
