@@ -213,6 +213,48 @@ typedef struct {            /* DEVICE arrays, caller-allocated, NULL = not wante
 int pbg_window_ld_decay(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                         uint32_t n_win, const pbg_decay_opts *opts, const pbg_decay_out *out, void *stream);
 
+/* Joint site-frequency spectrum and Fst per window and population pair (an extension; between
+ * populations the reference stops at dxy and the haplotype min-Dxy).  A context has populations
+ * 0 .. n_pops-1 of n_i samples; the pairs are the unordered i < j, numbered lexicographically:
+ * p = i*(2*n_pops - i - 1)/2 + (j - i - 1), n_pairs = n_pops*(n_pops-1)/2.  The sites of window
+ * [beg, end) are its rows with the segregating bit set (the set sfs_bins is taken over).  Such a
+ * row with sample bits t has a = popcount(t & pop_mask_i) and b = popcount(t & pop_mask_j); when
+ * the context has PBG_F_OUTGROUP and bit outidx of t is set, both flip: a -> n_i - a, b -> n_j - b
+ * (calc_sfs's flip).
+ *   cells  J_p[a][b] = the window's segregating rows with counts (a, b), int32.  A window's cells
+ *          are packed: pair p starts at off[p] = sum over q < p of (n_i(q)+1)*(n_j(q)+1), cell
+ *          (a, b) is at off[p] + a*(n_j+1) + b, and a window's block is C = off[n_pairs] cells
+ *          (pbg_jsfs_cells; at most 17,767: 64 populations over 126 samples).
+ *   diffs  three int64 per (window, pair), summed over the window's segregating rows:
+ *          SW_i = sum a(n_i-a), SW_j = sum b(n_j-b), SB = sum a(n_j-b) + b(n_i-a) -- the within- and
+ *          between-population pairwise-difference counts; the flip leaves them unchanged.
+ *   fst    Hudson's estimator as a ratio of sums, one double per (window, pair), exactly
+ *              pw_i = (double)SW_i / (double)(n_i*(n_i-1)/2)
+ *              pw_j = (double)SW_j / (double)(n_j*(n_j-1)/2)
+ *              pb   = (double)SB   / (double)(n_i*n_j)
+ *              fst  = 1.0 - (0.5 * (pw_i + pw_j)) / pb
+ *          with IEEE operations and no fused multiply-add, so it is reproducible from the integers;
+ *          a quiet NaN when n_i < 2, n_j < 2 or SB == 0.
+ * Windows with beg >= end give zero cells, zero diffs and NaN.  n_pops == 1 is valid: PBG_OK and
+ * nothing is written.  Integer atomics only, so two runs give the same bytes; no list of sites is
+ * kept, so a window of any length works and the call has no workspace.  Asynchronous like
+ * pbg_window_stats and free to interleave with it and with pbg_window_ld_decay on one stream (it
+ * shares none of their state).  A window outside [0, n_rows] is not read: it gives the outputs of
+ * an empty window and the next pbg_check returns PBG_E_RANGE.  PBG_E_ARG for a null ctx, rows,
+ * wins, opts or out, for outidx outside 0..n_samples-1 when the context has PBG_F_OUTGROUP, when
+ * n_win * C or n_win * n_pairs passes int32 indexing, and for a context whose pop_n[i] is not the
+ * number of samples in pop_mask[i] (the cell layout is built from pop_n). */
+typedef struct { int32_t outidx, _pad; } pbg_jsfs_opts;   /* the flip applies only with PBG_F_OUTGROUP */
+typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int32_t *cells;            /* [n_win * pbg_jsfs_cells()]  */
+    int64_t *diffs;            /* [n_win * n_pairs * 3]  SW_i, SW_j, SB */
+    double  *fst;              /* [n_win * n_pairs]      */
+} pbg_jsfs_out;
+int pbg_jsfs_cells(const pbg_ctx *ctx);                      /* C; 0 for one population (or a null ctx) */
+int pbg_jsfs_pair_offset(const pbg_ctx *ctx, int i, int j);  /* off[p] for i < j; PBG_E_ARG otherwise */
+int pbg_window_jsfs(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                    uint32_t n_win, const pbg_jsfs_opts *opts, const pbg_jsfs_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -231,7 +273,11 @@ enum { PBG_CMD_SNP = 0, PBG_CMD_HAPLO = 1, PBG_CMD_DIVERGE = 2, PBG_CMD_TREE = 3
 
 typedef struct {
     int32_t  cmd;          /* PBG_CMD_*                                                   */
-    int32_t  output;       /* -o                                                          */
+    int32_t  output;       /* -o; sfs: bit 0 = --theta, bit 1 = --joint (a streamed run also runs
+                              pbg_window_jsfs on the command's windows with outidx and appends,
+                              per pair i < j, "fst[popI,popJ]:" (NA for NaN) and "jsfs[popI,popJ]:"
+                              the pair's cells, comma-separated in cell order, after the
+                              reference's columns and --theta's)                              */
     int32_t  min_sites;    /* -k                                                          */
     int32_t  min_snps;     /* ld -n                                                       */
     int32_t  min_freq;     /* ld 1 / 2 (-e)                                               */
@@ -269,7 +315,8 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
 /* print_<stat> for windows whose results were copied to the HOST: `host_out` holds host
  * arrays laid out as pbg_window_out, `wbeg`/`wend` the contig coordinates the reference
  * prints (+1 applied here).  Same return convention as pbg_run.  It takes no decay arrays and
- * prints the reference's columns only, whatever the command's decay_bin says.              */
+ * prints the reference's columns only, whatever the command's decay_bin says; no joint-spectrum
+ * arrays either, so sfs output bit 1 (--joint) adds nothing here.                          */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

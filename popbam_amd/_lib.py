@@ -29,7 +29,8 @@ EXPORTS = ["pbg_create", "pbg_destroy", "pbg_last_error", "pbg_row_bytes", "pbg_
            "pbg_device_count", "pbg_call_sites", "pbg_window_stats", "pbg_check", "pbg_run", "pbg_take_text",
            "pbg_format", "pbg_build_info", "pbg_set_kernel_timing", "pbg_kernel_time", "pbg_call_time", "pbg_synth_max_keys",
            "pbg_synth_pileup", "pbg_stream_open", "pbg_stream_push", "pbg_stream_push_compact", "pbg_stream_finish", "pbg_stream_text",
-           "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay"]
+           "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay",
+           "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs"]
 
 PBG_DECAY_MAX_BINS = 256
 
@@ -90,6 +91,14 @@ class PbgDecayOut(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("r2_sum", C.c_void_p), ("n_var", C.c_void_p)]
 
 
+class PbgJsfsOpts(C.Structure):
+    _fields_ = [("outidx", C.c_int32), ("_pad", C.c_int32)]
+
+
+class PbgJsfsOut(C.Structure):
+    _fields_ = [("cells", C.c_void_p), ("diffs", C.c_void_p), ("fst", C.c_void_p)]
+
+
 class PbgStreamProf(C.Structure):
     _fields_ = [("h2d_bytes", C.c_uint64), ("pieces", C.c_uint32), ("chunks", C.c_uint32),
                 ("pinned_chunks", C.c_uint32), ("_pad", C.c_uint32), ("ms_stage", C.c_double),
@@ -143,6 +152,12 @@ def load(torch_first: bool = True):
     lib.pbg_window_stats.restype = C.c_int
     lib.pbg_window_ld_decay.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgDecayOpts), P(PbgDecayOut), vp]
     lib.pbg_window_ld_decay.restype = C.c_int
+    lib.pbg_jsfs_cells.argtypes = [vp]
+    lib.pbg_jsfs_cells.restype = C.c_int
+    lib.pbg_jsfs_pair_offset.argtypes = [vp, C.c_int, C.c_int]
+    lib.pbg_jsfs_pair_offset.restype = C.c_int
+    lib.pbg_window_jsfs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgJsfsOpts), P(PbgJsfsOut), vp]
+    lib.pbg_window_jsfs.restype = C.c_int
     lib.pbg_build_info.argtypes = []
     lib.pbg_build_info.restype = C.c_char_p
     lib.pbg_check.argtypes = [vp, vp]

@@ -70,8 +70,23 @@ hipError_t upload(T **dst, const std::vector<T> &v) {
 
 }  // namespace
 
+namespace {
+// off[p] of every pair i < j in lexicographic order, and off[n_pairs] = C (include/popbam_gpu.h)
+std::vector<int32_t> jsfs_offsets(const pbg::DevParams &dp) {
+    std::vector<int32_t> off;
+    int32_t at = 0;
+    for (int i = 0; i < dp.npops; ++i)
+        for (int j = i + 1; j < dp.npops; ++j) {
+            off.push_back(at);
+            at += (dp.pop_n[i] + 1) * (dp.pop_n[j] + 1);
+        }
+    off.push_back(at);
+    return off;
+}
+}  // namespace
+
 namespace pbg {
-extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay;
+extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs;
 }
 
 namespace {
@@ -318,7 +333,8 @@ void pbg_destroy(pbg_ctx *c) {
                     (void *)c->d_fbeta, (void *)c->d_lb, (void *)c->d_oe, c->d_scantab, (void *)c->d_err, (void *)c->d_ws, (void *)c->d_wsoff, (void *)c->d_zns,
                     (void *)c->deep.sites, (void *)c->deep.tasks, (void *)c->deep.info, (void *)c->deep.count,
                     (void *)c->deep.blk_cnt, (void *)c->deep.raw, (void *)c->deep.pend,
-                    (void *)c->d_segcnt, (void *)c->d_synth, (void *)c->d_decay_used})
+                    (void *)c->d_segcnt, (void *)c->d_synth, (void *)c->d_decay_used, (void *)c->jsfs.d_pairs,
+                    (void *)c->jsfs.d_groups})
         if (p) (void)hipFree(p);
     for (auto &t : c->tmpl) (void)hipFree(t.second);
     for (auto *v : {&c->ev, &c->evc})
@@ -448,7 +464,8 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 }
 
 const char *pbg_build_info(void) {
-    const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay});
+    const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay,
+                               pbg::kBuildKind_jsfs});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -692,6 +709,74 @@ int pbg_window_ld_decay(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg
     A.n_var = out->n_var;
     HIPCHK(c, hipMemsetAsync(A.pool_used, 0, 8, (hipStream_t)stream));
     HIPCHK(c, pbg::launch_window_decay(c->row_bytes, c->dp, c->dt, rows, n_rows, n_win, A, lds, (hipStream_t)stream));
+    return PBG_OK;
+}
+
+int pbg_jsfs_cells(const pbg_ctx *c) { return c ? jsfs_offsets(c->dp).back() : 0; }
+
+int pbg_jsfs_pair_offset(const pbg_ctx *c, int i, int j) {
+    if (!c) return PBG_E_ARG;
+    const int np = c->dp.npops;
+    if (i < 0 || j <= i || j >= np) return PBG_E_ARG;
+    return jsfs_offsets(c->dp)[(size_t)(i * (2 * np - i - 1) / 2 + (j - i - 1))];
+}
+
+int pbg_window_jsfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                    const pbg_jsfs_opts *o, const pbg_jsfs_out *out, void *stream) {
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    const bool flip = (c->dp.flag & PBG_F_OUTGROUP) != 0;
+    if (flip && (o->outidx < 0 || o->outidx >= c->dp.n)) return fail(c, PBG_E_ARG, "jsfs: outidx must be a sample index");
+    const int np = c->dp.npops;
+    if (np < 2 || n_win == 0) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    pbg_ctx::JsfsPlan &pl = c->jsfs;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!pl.built) {
+        // the counts are popcounts within the masks, so the cell layout (from pop_n) needs them equal
+        for (int i = 0; i < np; ++i)
+            if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
+                return fail(c, PBG_E_ARG, "jsfs: pop_n must be the number of samples in pop_mask");
+        const std::vector<int32_t> off = jsfs_offsets(c->dp);
+        std::vector<uint32_t> pairs;
+        for (int i = 0; i < np; ++i)
+            for (int j = i + 1; j < np; ++j) pairs.push_back(pbg::jsfs_pair_word((uint32_t)off[pairs.size()], i, j));
+        // groups of consecutive pairs whose cells fit the LDS histogram (one pair always does)
+        std::vector<int32_t> groups{0};
+        int32_t lds_cells = 0;
+        for (size_t p = 0, g0 = 0; p < pairs.size(); ++p) {
+            if (off[p + 1] - off[g0] > pbg::kJsfsLdsCells) {
+                groups.push_back((int32_t)p);
+                g0 = p;
+            }
+            lds_cells = std::max(lds_cells, off[p + 1] - off[g0]);
+        }
+        groups.push_back((int32_t)pairs.size());
+        HIPCHK(c, hipMalloc((void **)&pl.d_pairs, pairs.size() * 4));
+        HIPCHK(c, hipMalloc((void **)&pl.d_groups, groups.size() * 4));
+        HIPCHK(c, hipMemcpy(pl.d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(pl.d_groups, groups.data(), groups.size() * 4, hipMemcpyHostToDevice));
+        pl.n_pairs = (int32_t)pairs.size();
+        pl.n_groups = (int32_t)groups.size() - 1;
+        pl.n_cells = off.back();
+        pl.lds_cells = lds_cells;
+        pl.built = true;
+    }
+    if ((uint64_t)n_win * (uint64_t)pl.n_cells > 0x7FFFFFFFull || (uint64_t)n_win * (uint64_t)pl.n_pairs > 0x7FFFFFFFull)
+        return fail(c, PBG_E_ARG, "jsfs: too many windows");
+    pbg::JsfsArgs A{};
+    A.wins = wins;
+    A.pairs = pl.d_pairs;
+    A.groups = pl.d_groups;
+    A.n_pairs = pl.n_pairs;
+    A.n_groups = pl.n_groups;
+    A.n_cells = pl.n_cells;
+    A.lds_cells = pl.lds_cells;
+    A.outidx = flip ? o->outidx : -1;
+    A.err = c->d_err;
+    A.cells = out->cells;
+    A.diffs = out->diffs;
+    A.fst = out->fst;
+    HIPCHK(c, pbg::launch_window_jsfs(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
     return PBG_OK;
 }
 

@@ -278,6 +278,25 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                         o.i(w.sfs_bins[i][j]);
                     }
                 }
+            // --joint: per pair i < j Hudson's Fst and the joint spectrum's (n_i+1)*(n_j+1) cells
+            // in cell order, after the reference's columns and --theta's
+            if ((c.output & 2) && np > 1 && w.jsfs_fst.size() == (size_t)np * (np - 1) / 2 && (int)w.jsfs_n.size() == np) {
+                const std::vector<int32_t> &pop_n = w.jsfs_n;
+                size_t p = 0, at = 0;
+                for (int i = 0; i < np - 1; i++)
+                    for (int j = i + 1; j < np; j++, p++) {
+                        const size_t cells = (size_t)(pop_n[i] + 1) * (pop_n[j] + 1);
+                        if (at + cells > w.jsfs_cells.size()) break;
+                        o.t("\tfst[" + pn(c, i) + "," + pn(c, j) + "]:\t");
+                        if (std::isnan(w.jsfs_fst[p])) o.na(); else o.f(w.jsfs_fst[p]);
+                        o.t("\tjsfs[" + pn(c, i) + "," + pn(c, j) + "]:\t");
+                        for (size_t k = 0; k < cells; k++) {
+                            if (k) o.t(",");
+                            o.i(w.jsfs_cells[at + k]);
+                        }
+                        at += cells;
+                    }
+            }
             break;
         case PBG_CMD_LD:  // print_ld pop_ld.cpp:650-712
             for (int i = 0; i < np; i++) {

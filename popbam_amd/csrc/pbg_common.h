@@ -334,6 +334,27 @@ struct DecayArgs {
     uint32_t pool_div;                    // PBG_BOUNDS store checks, as StatsArgs::pool_div
 };
 
+// window_jsfs_kernel (pbg_window_jsfs): joint site-frequency spectrum, pairwise-difference counts
+// and Fst per (window, population pair).  A window's histogram lives in LDS; pairs are processed in
+// groups of consecutive pairs whose cells fit kJsfsLdsCells (one pair is at most 64 * 64 = 4,096
+// cells), the window's rows streamed once per group.
+constexpr int kJsfsLdsCells = 8192;   // 32 KiB of histogram per workgroup (beside 21.3 KiB static)
+constexpr int kJsfsCntBytes = 1024;   // per wave: the staged per-population counts of a batch of rows
+// pair p of the context: off[p] | i << 15 | j << 21 (off < 17,767 < 2^15; i, j < 64)
+__host__ __device__ inline uint32_t jsfs_pair_word(uint32_t off, int i, int j) { return off | (uint32_t)i << 15 | (uint32_t)j << 21; }
+struct JsfsArgs {
+    const pbg_window *wins;
+    const uint32_t *pairs;    // [n_pairs] jsfs_pair_word
+    const int32_t *groups;    // [n_groups + 1] first pair of each group
+    int32_t n_pairs, n_groups, n_cells;   // n_cells = C
+    int32_t lds_cells;        // dynamic LDS in cells: the largest group
+    int32_t outidx;           // -1: no flip
+    int *err;
+    int32_t *cells;           // [n_win * C] or null
+    int64_t *diffs;           // [n_win * n_pairs * 3] or null
+    double *fst;              // [n_win * n_pairs] or null
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -470,5 +491,8 @@ hipError_t launch_window_stats(int row_bytes, const DevParams &P, const DevTable
 size_t decay_lds_bytes(int row_bytes, const DevParams &P, DecayArgs &A);
 hipError_t launch_window_decay(int row_bytes, const DevParams &P, const DevTables &T, const void *rows,
                                uint32_t n_rows, uint32_t n_win, const DecayArgs &A, size_t lds, hipStream_t stream);
+// jsfs_kernel.hip (dynamic LDS: A.lds_cells * 4 bytes)
+hipError_t launch_window_jsfs(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                              const JsfsArgs &A, hipStream_t stream);
 
 }  // namespace pbg

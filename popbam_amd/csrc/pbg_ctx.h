@@ -48,6 +48,8 @@ struct StreamBufs {
     size_t out_cap = 0;
     void *d_decay = nullptr;             // ld --decay: pairs | r2_sum of one command
     size_t decay_cap = 0;
+    void *d_jsfs = nullptr;              // sfs --joint: cells | fst of one block of windows
+    size_t jsfs_cap = 0;
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };
@@ -97,6 +99,15 @@ struct pbg_ctx {
     };
     std::vector<DecayPlan> decay_plans;
     unsigned long long *d_decay_used = nullptr;
+    // pbg_window_jsfs: the context's pair table and pair groups (pbg::JsfsArgs), built and uploaded by
+    // the first call; the call has no other state and touches neither plan cache nor the workspace
+    struct JsfsPlan {
+        bool built = false;
+        int32_t n_pairs = 0, n_groups = 0, n_cells = 0, lds_cells = 0;
+        uint32_t *d_pairs = nullptr;
+        int32_t *d_groups = nullptr;
+    };
+    JsfsPlan jsfs;
     // samples deeper than the register sort width (call kernel): queues + parked info bytes
     pbg::DeepBufs deep{};
     size_t deep_sites_cap = 0, deep_info_cap = 0;

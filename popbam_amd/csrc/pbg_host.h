@@ -36,6 +36,11 @@ struct WindowHost {
     // [p * decay_bins + k] (pbg_window_ld_decay); empty when the caller has none (pbg_format)
     std::vector<int64_t> decay_pairs;
     std::vector<double> decay_sum;
+    // sfs --joint (pbg_cmd.output bit 1): Fst of pair p at [p], the window's packed cells
+    // (pbg_window_jsfs) and the population sizes that shape them; empty when the caller has none
+    // (pbg_format)
+    std::vector<double> jsfs_fst;
+    std::vector<int32_t> jsfs_cells, jsfs_n;
 };
 
 // print_nucdiv / print_sfs / print_ld / print_diverge / print_haplo (TSV, byte-identical)

@@ -282,6 +282,8 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
     if (cmd == "diverge" && tk.present('t')) o.flag |= BAM_SUBSTITUTE;
     if (cmd == "sfs" && std::find(argv.begin(), argv.end(), std::string("--theta")) != argv.end())
         o.output |= 1;   // extension: S, theta_W and the spectrum after the reference's columns
+    if (cmd == "sfs" && std::find(argv.begin(), argv.end(), std::string("--joint")) != argv.end())
+        o.output |= 2;   // extension: Fst and the joint spectrum of every population pair after those
     if (cmd == "ld" && tk.present('e')) o.min_freq = 2;
     if (cmd == "snp" && tk.present('v')) o.flag |= BAM_VARIANT;
     if (cmd == "snp" && tk.present('z')) o.flag |= BAM_HETEROZYGOTE;

@@ -390,12 +390,52 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         HIPCHK(c, d2h(h_dsum.data(), dout.r2_sum, szk * 8));
     }
     HIPCHK(c, hipStreamSynchronize(s));
+    // sfs --joint: the joint-spectrum kernel over the same windows (its columns follow the
+    // reference's and --theta's), a block of windows at a time so that the device and the host copy
+    // of the cells stay at kJsfsStage bytes each however many windows and populations there are
+    const bool joint = stats == PBG_S_SFS && (cmd->output & 2) && np > 1;
+    const size_t jC = joint ? (size_t)pbg_jsfs_cells(c) : 0, jP = (size_t)np * (np - 1) / 2;
+    constexpr size_t kJsfsStage = 64u << 20;
+    const uint32_t jblock = joint ? (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kJsfsStage / (jC * 4 + jP * 8))) : 0;
+    std::vector<int32_t> h_jcells;
+    std::vector<double> h_jfst;
+    uint32_t j0 = 0, j1 = 0;   // the windows of the block on the host
+    auto joint_block = [&](uint32_t first) -> int {
+        const uint32_t cnt = std::min(jblock, nw - first);
+        const size_t b_cells = al((size_t)jblock * jC * 4), need_j = b_cells + (size_t)jblock * jP * 8;
+        if (c->sb.jsfs_cap < need_j) {
+            if (c->sb.d_jsfs) HIPCHK(c, hipFree(c->sb.d_jsfs));
+            c->sb.d_jsfs = nullptr;
+            c->sb.jsfs_cap = 0;
+            HIPCHK(c, hipMalloc(&c->sb.d_jsfs, need_j));
+            c->sb.jsfs_cap = need_j;
+        }
+        const pbg_jsfs_opts jopt{cmd->outidx, 0};
+        const pbg_jsfs_out jout{(int32_t *)c->sb.d_jsfs, nullptr, (double *)((char *)c->sb.d_jsfs + b_cells)};
+        int jrc = pbg_window_jsfs(c, d_rows, dsites, d_win + first, cnt, &jopt, &jout, s);
+        if (jrc) return jrc;
+        if ((jrc = pbg_check(c, s))) return jrc;
+        h_jcells.resize((size_t)cnt * jC);
+        h_jfst.resize((size_t)cnt * jP);
+        HIPCHK(c, d2h(h_jcells.data(), jout.cells, h_jcells.size() * 4));
+        HIPCHK(c, d2h(h_jfst.data(), jout.fst, h_jfst.size() * 8));
+        HIPCHK(c, hipStreamSynchronize(s));
+        j0 = first;
+        j1 = first + cnt;
+        return PBG_OK;
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
         return std::vector<T>(v.begin() + off, v.begin() + off + cnt);
     };
     for (uint32_t i = 0; i < nw; ++i) {
+        if (joint) {
+            if (i >= j1 && (rc = joint_block(i))) return rc;
+            wh.jsfs_fst = slice(h_jfst, (size_t)(i - j0) * jP, jP);
+            wh.jsfs_cells = slice(h_jcells, (size_t)(i - j0) * jC, jC);
+            wh.jsfs_n.assign(c->dp.pop_n, c->dp.pop_n + np);
+        }
         wh.beg = win[i].first;
         wh.end = win[i].second;
         wh.num_sites = h_ns[i];
@@ -442,7 +482,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay})
+    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay, b.d_jsfs})
         if (p) (void)hipFree(p);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

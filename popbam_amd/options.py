@@ -189,6 +189,8 @@ def parse_args(cmd: str, argv: list[str]) -> Options:
         o.flag |= BAM_SUBSTITUTE
     if cmd == "sfs" and "--theta" in argv:
         o.output |= 1   # extension: append S, theta_W and the spectrum (print_sfs never prints them)
+    if cmd == "sfs" and "--joint" in argv:
+        o.output |= 2   # extension: append Fst and the joint spectrum of every population pair
     if cmd == "ld" and "e" in present:
         o.min_freq = 2
     if cmd == "snp" and "v" in present:

@@ -178,6 +178,46 @@ class LdDecay:
             hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
+class JointSfs:
+    """pbg_window_jsfs: the joint site-frequency spectrum, the pairwise-difference counts and
+    Hudson's Fst per window and population pair i < j.  Owns the three device arrays --
+    cells[n_win, C] (int32, C = pbg_jsfs_cells: pair p's (n_i+1) x (n_j+1) block at pair_offset),
+    diffs[n_win, n_pairs, 3] (int64: SW_i, SW_j, SB), fst[n_win, n_pairs] (float64) -- and runs
+    on a HotPath's rows and windows, or on any rows tensor with a window list.  `outidx` counts
+    only when the context has PBG_F_OUTGROUP."""
+
+    def __init__(self, ctx: _lib.Context, n_win: int, outidx: int = 0, device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        np_ = ctx.params.n_pops
+        self.n_pairs = np_ * (np_ - 1) // 2
+        self.n_cells = ctx.lib.pbg_jsfs_cells(ctx.h)
+        self.opts = _lib.PbgJsfsOpts(outidx, 0)
+        self.cells = torch.zeros((n_win, self.n_cells), dtype=torch.int32, device=device)
+        self.diffs = torch.zeros((n_win, self.n_pairs, 3), dtype=torch.int64, device=device)
+        self.fst = torch.zeros((n_win, self.n_pairs), dtype=torch.float64, device=device)
+        self.out = _lib.PbgJsfsOut(_ptr(self.cells), _ptr(self.diffs), _ptr(self.fst))
+
+    def pair_offset(self, i: int, j: int) -> int:
+        return self.ctx.check(self.ctx.lib.pbg_jsfs_pair_offset(self.ctx.h, i, j), "pbg_jsfs_pair_offset")
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_jsfs(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                            C.byref(self.opts), C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_jsfs")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", outidx: int = 0, stream=None) -> "JointSfs":
+        """The joint spectra of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, outidx, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 
