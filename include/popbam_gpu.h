@@ -255,6 +255,61 @@ int pbg_jsfs_pair_offset(const pbg_ctx *ctx, int i, int j);  /* off[p] for i < j
 int pbg_window_jsfs(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                     uint32_t n_win, const pbg_jsfs_opts *opts, const pbg_jsfs_out *out, void *stream);
 
+/* Patterson's D (ABBA-BABA) and the windowed f_d (Martin et al. 2015) and f_dM (Malinsky et al.
+ * 2015) per window and population triple (an extension).  A triple (P1, P2, P3) names three
+ * distinct populations of the context, of n1, n2, n3 samples; the ancestral state comes from the
+ * context's outgroup flip.  The sites of window [beg, end) are its rows with the segregating bit set
+ * (the set pbg_window_jsfs and sfs_bins are taken over).  Such a row with sample bits t has
+ * a = popcount(t & pop_mask_P1), b and c alike for P2 and P3; when the context has PBG_F_OUTGROUP
+ * and bit outidx of t is set, all three flip: a -> n1 - a, b -> n2 - b, c -> n3 - c (calc_sfs's
+ * flip).  The derived frequencies are p1 = a/n1, p2 = b/n2, p3 = c/n3.
+ *   sums   six int64 per (window, triple), each the sum of an integer term over the rows named:
+ *            0 ABBA  (n1-a)*b*c         all rows                          = n1*n2*n3 * (1-p1) p2 p3
+ *            1 BABA  a*(n2-b)*c         all rows                          = n1*n2*n3 * p1 (1-p2) p3
+ *            2 FD2   b*(b*n1 - a*n2)    rows with b*n3 >= c*n2 (donor P2) = n1*n2^2  * p2 (p2 - p1)
+ *            3 FD3   c*(c*n1 - a*n3)    rows with b*n3 <  c*n2 (donor P3) = n1*n3^2  * p3 (p3 - p1)
+ *            4 GD1   a*(a*n2 - b*n1)    rows with a*n3 >= c*n1 (donor P1) = n2*n1^2  * p1 (p1 - p2)
+ *            5 GD3   c*(c*n2 - b*n3)    rows with a*n3 <  c*n1 (donor P3) = n2*n3^2  * p3 (p3 - p2)
+ *          2 and 3 are Martin's S(P1, PD, PD, O) with PD the one of P2 and P3 of the higher derived
+ *          frequency at the site (a tie goes to P2); 4 and 5 are Malinsky's -S(PD, P2, PD, O) with
+ *          PD the higher of P1 and P3 (a tie goes to P1).  2 to 5 are signed.  A term stays below
+ *          2^21, so no window overflows.
+ *   d, fd, fdm   one double each per (window, triple), from the integers (products in int64)
+ *          with exactly these IEEE operations and no fused multiply-add:
+ *              num  = (double)(s0 - s1) / (double)(n1*n2*n3)
+ *              den  = (double)s2 / (double)(n1*n2*n2) + (double)s3 / (double)(n1*n3*n3)
+ *              den2 = (double)s4 / (double)(n2*n1*n1) + (double)s5 / (double)(n2*n3*n3)
+ *              d    = (double)(s0 - s1) / (double)(s0 + s1)       a quiet NaN when s0 + s1 == 0
+ *              fd   = num / den                                   a quiet NaN when den == 0.0
+ *              fdm  = s0 >= s1 ? num / den : num / den2           a quiet NaN when that denominator == 0.0
+ * Element (w, t) of d, fd, fdm is at w * n_triples + t, its sums at (w * n_triples + t) * 6.  Any
+ * order of a triple's members is valid, and so is listing a triple more than once.  D is meaningful
+ * only when none of the three populations contains the outgroup sample; such a triple is computed
+ * as defined all the same.  Windows with beg >= end give zero sums and NaN.  n_triples == 0 is
+ * valid: PBG_OK and nothing is written.  A NULL member of pbg_dstat_out is skipped.  Integer sums
+ * only (shuffles and integer LDS atomics), so two runs give the same bytes; no list of sites is
+ * kept, so a window of any length works and the call has no workspace.  The triple list is a HOST
+ * array, read before the call returns; the context keeps the device copies of the lists it has
+ * seen, by content.  Asynchronous like pbg_window_stats and free to interleave with it, with
+ * pbg_window_ld_decay and with pbg_window_jsfs on one stream (it shares none of their state).  A
+ * window outside [0, n_rows] is not read: it gives the outputs of an empty window and the next
+ * pbg_check returns PBG_E_RANGE.  PBG_E_ARG for a null ctx, rows, wins, opts or out, for n_triples
+ * < 0 or > PBG_DSTAT_MAX_TRIPLES, for a null triples with n_triples > 0, for a population index
+ * outside 0..n_pops-1, for a triple whose three populations are not distinct, for outidx outside
+ * 0..n_samples-1 when the context has PBG_F_OUTGROUP (without the flag outidx is ignored), and for a
+ * context whose pop_n[i] is not the number of samples in pop_mask[i]. */
+#define PBG_DSTAT_MAX_TRIPLES 4096
+typedef struct { int32_t p1, p2, p3; } pbg_triple;
+typedef struct { int32_t outidx, n_triples; const pbg_triple *triples; /* HOST array */ } pbg_dstat_opts;
+typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int64_t *sums;             /* [n_win * n_triples * 6] */
+    double  *d;                /* [n_win * n_triples]     */
+    double  *fd;               /* same */
+    double  *fdm;              /* same */
+} pbg_dstat_out;
+int pbg_window_dstat(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                     uint32_t n_win, const pbg_dstat_opts *opts, const pbg_dstat_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -277,7 +332,14 @@ typedef struct {
                               pbg_window_jsfs on the command's windows with outidx and appends,
                               per pair i < j, "fst[popI,popJ]:" (NA for NaN) and "jsfs[popI,popJ]:"
                               the pair's cells, comma-separated in cell order, after the
-                              reference's columns and --theta's)                              */
+                              reference's columns and --theta's); bit 2 = --dstat (with three or
+                              more populations a streamed run also runs pbg_window_dstat with
+                              outidx over all triples (i, j, k), i < j, k not i or j, in
+                              lexicographic order and appends, per triple, "D[popI,popJ,popK]:",
+                              "fd[popI,popJ,popK]:", "fdM[popI,popJ,popK]:" (NA for NaN) and
+                              "dsum[popI,popJ,popK]:" the six sums, comma-separated, after
+                              --joint's columns; more than PBG_DSTAT_MAX_TRIPLES triples, i.e.
+                              more than 21 populations: PBG_E_ARG)                            */
     int32_t  min_sites;    /* -k                                                          */
     int32_t  min_snps;     /* ld -n                                                       */
     int32_t  min_freq;     /* ld 1 / 2 (-e)                                               */
@@ -316,7 +378,8 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
  * arrays laid out as pbg_window_out, `wbeg`/`wend` the contig coordinates the reference
  * prints (+1 applied here).  Same return convention as pbg_run.  It takes no decay arrays and
  * prints the reference's columns only, whatever the command's decay_bin says; no joint-spectrum
- * arrays either, so sfs output bit 1 (--joint) adds nothing here.                          */
+ * arrays and no D-statistic arrays either, so sfs output bits 1 (--joint) and 2 (--dstat) add
+ * nothing here.                                                                             */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

@@ -30,9 +30,10 @@ EXPORTS = ["pbg_create", "pbg_destroy", "pbg_last_error", "pbg_row_bytes", "pbg_
            "pbg_format", "pbg_build_info", "pbg_set_kernel_timing", "pbg_kernel_time", "pbg_call_time", "pbg_synth_max_keys",
            "pbg_synth_pileup", "pbg_stream_open", "pbg_stream_push", "pbg_stream_push_compact", "pbg_stream_finish", "pbg_stream_text",
            "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay",
-           "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs"]
+           "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs", "pbg_window_dstat"]
 
 PBG_DECAY_MAX_BINS = 256
+PBG_DSTAT_MAX_TRIPLES = 4096
 
 
 class PbgParams(C.Structure):
@@ -99,6 +100,18 @@ class PbgJsfsOut(C.Structure):
     _fields_ = [("cells", C.c_void_p), ("diffs", C.c_void_p), ("fst", C.c_void_p)]
 
 
+class PbgTriple(C.Structure):
+    _fields_ = [("p1", C.c_int32), ("p2", C.c_int32), ("p3", C.c_int32)]
+
+
+class PbgDstatOpts(C.Structure):
+    _fields_ = [("outidx", C.c_int32), ("n_triples", C.c_int32), ("triples", C.POINTER(PbgTriple))]   # a HOST array
+
+
+class PbgDstatOut(C.Structure):
+    _fields_ = [("sums", C.c_void_p), ("d", C.c_void_p), ("fd", C.c_void_p), ("fdm", C.c_void_p)]
+
+
 class PbgStreamProf(C.Structure):
     _fields_ = [("h2d_bytes", C.c_uint64), ("pieces", C.c_uint32), ("chunks", C.c_uint32),
                 ("pinned_chunks", C.c_uint32), ("_pad", C.c_uint32), ("ms_stage", C.c_double),
@@ -158,6 +171,8 @@ def load(torch_first: bool = True):
     lib.pbg_jsfs_pair_offset.restype = C.c_int
     lib.pbg_window_jsfs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgJsfsOpts), P(PbgJsfsOut), vp]
     lib.pbg_window_jsfs.restype = C.c_int
+    lib.pbg_window_dstat.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgDstatOpts), P(PbgDstatOut), vp]
+    lib.pbg_window_dstat.restype = C.c_int
     lib.pbg_build_info.argtypes = []
     lib.pbg_build_info.restype = C.c_char_p
     lib.pbg_check.argtypes = [vp, vp]

@@ -139,6 +139,8 @@ def run(cmd: str, argv: list[str], device: int = 0, rank: int = 0, world: int = 
         if o.flag & opt.BAM_OUTGROUP and cmd in ("sfs", "diverge", "snp") and o.outgroup not in sm.samples:
             # checked right after bam_smpl_add (pop_sfs.cpp:37-50, pop_diverge.cpp:37-50, pop_snp.cpp:36-49)
             raise opt.PopbamError(f"Specified outgroup {o.outgroup} not found")
+        if cmd == "sfs" and o.output & 4:
+            opt.dstat_triples(len(sm.pops))   # fatal past PBG_DSTAT_MAX_TRIPLES, before any GPU work
         refid = opt.get_refid(header) if cmd == "tree" else ""
         refs = bam.refs
         names, lengths = [r[0] for r in refs], [r[1] for r in refs]

@@ -86,7 +86,7 @@ std::vector<int32_t> jsfs_offsets(const pbg::DevParams &dp) {
 }  // namespace
 
 namespace pbg {
-extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs;
+extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat;
 }
 
 namespace {
@@ -337,6 +337,8 @@ void pbg_destroy(pbg_ctx *c) {
                     (void *)c->jsfs.d_groups})
         if (p) (void)hipFree(p);
     for (auto &t : c->tmpl) (void)hipFree(t.second);
+    for (auto &l : c->dstat_lists)
+        if (l.d) (void)hipFree(l.d);
     for (auto *v : {&c->ev, &c->evc})
         for (auto &e : *v) {
             (void)hipEventDestroy(e.first);
@@ -465,7 +467,7 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 
 const char *pbg_build_info(void) {
     const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay,
-                               pbg::kBuildKind_jsfs});
+                               pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -777,6 +779,67 @@ int pbg_window_jsfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_win
     A.diffs = out->diffs;
     A.fst = out->fst;
     HIPCHK(c, pbg::launch_window_jsfs(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    return PBG_OK;
+}
+
+int pbg_window_dstat(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                     const pbg_dstat_opts *o, const pbg_dstat_out *out, void *stream) {
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    if (o->n_triples < 0 || o->n_triples > PBG_DSTAT_MAX_TRIPLES)
+        return fail(c, PBG_E_ARG, "dstat: n_triples must be in [0, " + std::to_string(PBG_DSTAT_MAX_TRIPLES) + "]");
+    if (o->n_triples > 0 && !o->triples) return fail(c, PBG_E_ARG, "dstat: null triple list");
+    const bool flip = (c->dp.flag & PBG_F_OUTGROUP) != 0;
+    if (flip && (o->outidx < 0 || o->outidx >= c->dp.n)) return fail(c, PBG_E_ARG, "dstat: outidx must be a sample index");
+    const int np = c->dp.npops;
+    std::vector<uint32_t> words((size_t)o->n_triples);
+    for (int t = 0; t < o->n_triples; ++t) {
+        const pbg_triple &tr = o->triples[t];
+        if (tr.p1 < 0 || tr.p1 >= np || tr.p2 < 0 || tr.p2 >= np || tr.p3 < 0 || tr.p3 >= np)
+            return fail(c, PBG_E_ARG, "dstat: triple " + std::to_string(t) + " names a population outside 0.." + std::to_string(np - 1));
+        if (tr.p1 == tr.p2 || tr.p1 == tr.p3 || tr.p2 == tr.p3)
+            return fail(c, PBG_E_ARG, "dstat: the populations of triple " + std::to_string(t) + " are not distinct");
+        words[(size_t)t] = pbg::dstat_triple_word(tr.p1, tr.p2, tr.p3);
+    }
+    if (o->n_triples == 0 || n_win == 0) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    // the counts are popcounts within the masks and are parked as bytes: n - count needs pop_n to be them
+    for (int i = 0; i < np; ++i)
+        if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
+            return fail(c, PBG_E_ARG, "dstat: pop_n must be the number of samples in pop_mask");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the list's device copy, by content (pbg_ctx.h): written once, never overwritten
+    const uint32_t *d_words = nullptr;
+    for (size_t k = c->dstat_lists.size(); k-- > 0 && !d_words;)
+        if (c->dstat_lists[k].words == words) {
+            d_words = c->dstat_lists[k].d;
+            std::rotate(c->dstat_lists.begin() + k, c->dstat_lists.begin() + k + 1, c->dstat_lists.end());
+        }
+    if (!d_words) {
+        if (c->dstat_lists.size() >= 16) {
+            HIPCHK(c, hipFree(c->dstat_lists.front().d));   // waits for every launch that may read it
+            c->dstat_lists.erase(c->dstat_lists.begin());
+        }
+        uint32_t *d = nullptr;
+        HIPCHK(c, hipMalloc((void **)&d, words.size() * 4));
+        const hipError_t e = hipMemcpy(d, words.data(), words.size() * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            HIPCHK(c, e);
+        }
+        c->dstat_lists.push_back({std::move(words), d});
+        d_words = d;
+    }
+    pbg::DstatArgs A{};
+    A.wins = wins;
+    A.triples = d_words;
+    A.n_triples = o->n_triples;
+    A.outidx = flip ? o->outidx : -1;
+    A.err = c->d_err;
+    A.sums = out->sums;
+    A.d = out->d;
+    A.fd = out->fd;
+    A.fdm = out->fdm;
+    HIPCHK(c, pbg::launch_window_dstat(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
     return PBG_OK;
 }
 

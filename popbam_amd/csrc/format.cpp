@@ -297,6 +297,27 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                         at += cells;
                     }
             }
+            // --dstat: per triple (i, j, k) D, f_d, f_dM and the six sums they are formed from, after
+            // --joint's columns
+            if ((c.output & 4) && np > 2) {
+                const std::vector<pbg_triple> tr = dstat_triples(np);
+                if (w.dstat_d.size() == tr.size() && w.dstat_fd.size() == tr.size() && w.dstat_fdm.size() == tr.size() &&
+                    w.dstat_sums.size() == tr.size() * 6)
+                    for (size_t t = 0; t < tr.size(); t++) {
+                        const std::string lab = "[" + pn(c, tr[t].p1) + "," + pn(c, tr[t].p2) + "," + pn(c, tr[t].p3) + "]:\t";
+                        const std::pair<const char *, double> val[3] = {
+                            {"\tD", w.dstat_d[t]}, {"\tfd", w.dstat_fd[t]}, {"\tfdM", w.dstat_fdm[t]}};
+                        for (const auto &v : val) {
+                            o.t(v.first + lab);
+                            if (std::isnan(v.second)) o.na(); else o.f(v.second);
+                        }
+                        o.t("\tdsum" + lab);
+                        for (int k = 0; k < 6; k++) {
+                            if (k) o.t(",");
+                            o.i(w.dstat_sums[t * 6 + k]);
+                        }
+                    }
+            }
             break;
         case PBG_CMD_LD:  // print_ld pop_ld.cpp:650-712
             for (int i = 0; i < np; i++) {

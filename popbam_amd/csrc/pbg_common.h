@@ -355,6 +355,27 @@ struct JsfsArgs {
     double *fst;              // [n_win * n_pairs] or null
 };
 
+// window_dstat_kernel (pbg_window_dstat): ABBA-BABA sums, D, f_d and f_dM per (window, population
+// triple).  A window's six int64 sums per triple live in LDS ([6][group] so that a lane per triple
+// is conflict-free); lists longer than kDstatLdsTriples go in groups of that many consecutive
+// triples, the window's rows streamed once per group.
+constexpr int kDstatLdsTriples = 512;    // 24 KiB of sums per workgroup at most (beside 15.3 KiB static)
+constexpr int kDstatCntBytes = 1024;     // per wave: the staged per-population counts of a batch of rows
+constexpr int kDstatLaneTriples = 64;    // lists up to this long: a lane keeps one triple's sums in registers
+// triple (p1, p2, p3) of the call's list: p1 | p2 << 6 | p3 << 12 (populations < 64)
+__host__ __device__ inline uint32_t dstat_triple_word(int p1, int p2, int p3) {
+    return (uint32_t)p1 | (uint32_t)p2 << 6 | (uint32_t)p3 << 12;
+}
+struct DstatArgs {
+    const pbg_window *wins;
+    const uint32_t *triples;   // [n_triples] dstat_triple_word
+    int32_t n_triples;
+    int32_t outidx;            // -1: no flip
+    int *err;
+    int64_t *sums;             // [n_win * n_triples * 6] or null
+    double *d, *fd, *fdm;      // [n_win * n_triples] each, or null
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -494,5 +515,8 @@ hipError_t launch_window_decay(int row_bytes, const DevParams &P, const DevTable
 // jsfs_kernel.hip (dynamic LDS: A.lds_cells * 4 bytes)
 hipError_t launch_window_jsfs(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                               const JsfsArgs &A, hipStream_t stream);
+// dstat_kernel.hip (dynamic LDS: min(A.n_triples, kDstatLdsTriples) * 48 bytes)
+hipError_t launch_window_dstat(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                               const DstatArgs &A, hipStream_t stream);
 
 }  // namespace pbg

@@ -50,6 +50,8 @@ struct StreamBufs {
     size_t decay_cap = 0;
     void *d_jsfs = nullptr;              // sfs --joint: cells | fst of one block of windows
     size_t jsfs_cap = 0;
+    void *d_dstat = nullptr;             // sfs --dstat: sums | d | fd | fdm of one block of windows
+    size_t dstat_cap = 0;
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };
@@ -108,6 +110,15 @@ struct pbg_ctx {
         int32_t *d_groups = nullptr;
     };
     JsfsPlan jsfs;
+    // pbg_window_dstat: device copies of the triple lists seen so far, kept by content, most recent
+    // last.  A copy is written once, before its first launch, and never again, so a launch still
+    // running on any stream keeps reading what it was given; the oldest is dropped past 16 lists
+    // (hipFree waits for the device).  A list seen before costs no allocation and no copy.
+    struct DstatList {
+        std::vector<uint32_t> words;   // pbg::dstat_triple_word of every triple
+        uint32_t *d = nullptr;
+    };
+    std::vector<DstatList> dstat_lists;
     // samples deeper than the register sort width (call kernel): queues + parked info bytes
     pbg::DeepBufs deep{};
     size_t deep_sites_cap = 0, deep_info_cap = 0;

@@ -41,7 +41,22 @@ struct WindowHost {
     // (pbg_format)
     std::vector<double> jsfs_fst;
     std::vector<int32_t> jsfs_cells, jsfs_n;
+    // sfs --dstat (pbg_cmd.output bit 2): D, f_d, f_dM of triple t at [t] and its six sums at
+    // [t * 6] (pbg_window_dstat over dstat_triples(np)); empty when the caller has none (pbg_format)
+    std::vector<double> dstat_d, dstat_fd, dstat_fdm;
+    std::vector<int64_t> dstat_sums;
 };
+
+// sfs --dstat's triples of n_pops populations: all (i, j, k) with i < j and k neither, in
+// lexicographic order -- n_pops * (n_pops - 1) / 2 * (n_pops - 2) of them
+inline std::vector<pbg_triple> dstat_triples(int n_pops) {
+    std::vector<pbg_triple> t;
+    for (int i = 0; i < n_pops; ++i)
+        for (int j = i + 1; j < n_pops; ++j)
+            for (int k = 0; k < n_pops; ++k)
+                if (k != i && k != j) t.push_back({i, j, k});
+    return t;
+}
 
 // print_nucdiv / print_sfs / print_ld / print_diverge / print_haplo (TSV, byte-identical)
 void format_window(std::string &out, const pbg_cmd &cmd, int n_samples, int n_pops, uint32_t flag,

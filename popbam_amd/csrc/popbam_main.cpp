@@ -284,6 +284,8 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
         o.output |= 1;   // extension: S, theta_W and the spectrum after the reference's columns
     if (cmd == "sfs" && std::find(argv.begin(), argv.end(), std::string("--joint")) != argv.end())
         o.output |= 2;   // extension: Fst and the joint spectrum of every population pair after those
+    if (cmd == "sfs" && std::find(argv.begin(), argv.end(), std::string("--dstat")) != argv.end())
+        o.output |= 4;   // extension: D, f_d, f_dM and their sums of every population triple after those
     if (cmd == "ld" && tk.present('e')) o.min_freq = 2;
     if (cmd == "snp" && tk.present('v')) o.flag |= BAM_VARIANT;
     if (cmd == "snp" && tk.present('z')) o.flag |= BAM_HETEROZYGOTE;
@@ -662,6 +664,9 @@ std::string run(const std::string &cmd, const std::vector<std::string> &argv, in
         if (found < 0) throw Fatal{"Specified outgroup " + o.outgroup + " not found"};
         outidx = found;
     }
+    // sfs --dstat runs every triple (i, j, k), i < j, k neither: at most PBG_DSTAT_MAX_TRIPLES of them
+    if (cmd == "sfs" && (o.output & 4) && (long)npops * (npops - 1) / 2 * (npops - 2) > PBG_DSTAT_MAX_TRIPLES)
+        throw Fatal{"Too many populations for --dstat"};
     // pbg_params (engine.make_params): checked now, reported where the reference order puts them
     std::string param_err;
     if (o.max_depth < 0) param_err = "maximum read depth -x " + std::to_string(o.max_depth) + " must not be negative";

@@ -424,6 +424,48 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         j1 = first + cnt;
         return PBG_OK;
     };
+    // sfs --dstat: the D-statistic kernel over the same windows and all triples of the populations
+    // (its columns follow --joint's), in blocks of windows of at most kDstatStage bytes
+    const bool dstat = stats == PBG_S_SFS && (cmd->output & 4) && np > 2;
+    const std::vector<pbg_triple> dtr = dstat ? pbg::dstat_triples(np) : std::vector<pbg_triple>();
+    const size_t dT = dtr.size();
+    if (dT > PBG_DSTAT_MAX_TRIPLES) return fail(c, PBG_E_ARG, "Too many populations for --dstat");
+    constexpr size_t kDstatStage = 64u << 20;
+    const uint32_t dblock = dstat ? (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kDstatStage / (dT * 72))) : 0;
+    std::vector<int64_t> h_dsums;
+    std::vector<double> h_dd, h_dfd, h_dfdm;
+    uint32_t k0 = 0, k1 = 0;   // the windows of the block on the host
+    auto dstat_block = [&](uint32_t first) -> int {
+        const uint32_t cnt = std::min(dblock, nw - first);
+        const size_t per = (size_t)dblock * dT, need_d = per * 72;
+        if (c->sb.dstat_cap < need_d) {
+            if (c->sb.d_dstat) HIPCHK(c, hipFree(c->sb.d_dstat));
+            c->sb.d_dstat = nullptr;
+            c->sb.dstat_cap = 0;
+            HIPCHK(c, hipMalloc(&c->sb.d_dstat, need_d));
+            c->sb.dstat_cap = need_d;
+        }
+        const pbg_dstat_opts dopt{cmd->outidx, (int32_t)dT, dtr.data()};
+        int64_t *d_sums = (int64_t *)c->sb.d_dstat;
+        double *d_val = (double *)(d_sums + per * 6);
+        const pbg_dstat_out dout{d_sums, d_val, d_val + per, d_val + 2 * per};
+        int drc = pbg_window_dstat(c, d_rows, dsites, d_win + first, cnt, &dopt, &dout, s);
+        if (drc) return drc;
+        if ((drc = pbg_check(c, s))) return drc;
+        const size_t got = (size_t)cnt * dT;
+        h_dsums.resize(got * 6);
+        h_dd.resize(got);
+        h_dfd.resize(got);
+        h_dfdm.resize(got);
+        HIPCHK(c, d2h(h_dsums.data(), dout.sums, got * 48));
+        HIPCHK(c, d2h(h_dd.data(), dout.d, got * 8));
+        HIPCHK(c, d2h(h_dfd.data(), dout.fd, got * 8));
+        HIPCHK(c, d2h(h_dfdm.data(), dout.fdm, got * 8));
+        HIPCHK(c, hipStreamSynchronize(s));
+        k0 = first;
+        k1 = first + cnt;
+        return PBG_OK;
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
@@ -435,6 +477,13 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             wh.jsfs_fst = slice(h_jfst, (size_t)(i - j0) * jP, jP);
             wh.jsfs_cells = slice(h_jcells, (size_t)(i - j0) * jC, jC);
             wh.jsfs_n.assign(c->dp.pop_n, c->dp.pop_n + np);
+        }
+        if (dstat) {
+            if (i >= k1 && (rc = dstat_block(i))) return rc;
+            wh.dstat_sums = slice(h_dsums, (size_t)(i - k0) * dT * 6, dT * 6);
+            wh.dstat_d = slice(h_dd, (size_t)(i - k0) * dT, dT);
+            wh.dstat_fd = slice(h_dfd, (size_t)(i - k0) * dT, dT);
+            wh.dstat_fdm = slice(h_dfdm, (size_t)(i - k0) * dT, dT);
         }
         wh.beg = win[i].first;
         wh.end = win[i].second;
@@ -482,7 +531,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay, b.d_jsfs})
+    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay, b.d_jsfs, b.d_dstat})
         if (p) (void)hipFree(p);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

@@ -31,6 +31,7 @@ BAM_HEADERIN = 0x80
 CMD_IDS = {"snp": 0, "haplo": 1, "diverge": 2, "tree": 3, "nucdiv": 4, "ld": 5, "sfs": 6}
 
 DECAY_MAX_BINS = 256   # PBG_DECAY_MAX_BINS (include/popbam_gpu.h)
+DSTAT_MAX_TRIPLES = 4096   # PBG_DSTAT_MAX_TRIPLES
 
 
 class PopbamError(RuntimeError):
@@ -96,6 +97,14 @@ _INT_RE = re.compile(r"^\s*[+-]?\d+")
 
 def _is_int(s):
     return re.fullmatch(r"[+-]?\d+", s) is not None
+
+
+def dstat_triples(n_pops: int) -> list[tuple[int, int, int]]:
+    """The triples `sfs --dstat` runs: all (i, j, k) with i < j and k neither, in lexicographic
+    order.  More than DSTAT_MAX_TRIPLES of them (more than 21 populations) is fatal."""
+    if n_pops * (n_pops - 1) // 2 * (n_pops - 2) > DSTAT_MAX_TRIPLES:
+        raise PopbamError("Too many populations for --dstat")
+    return [(i, j, k) for i in range(n_pops) for j in range(i + 1, n_pops) for k in range(n_pops) if k not in (i, j)]
 
 
 def _is_float(s):
@@ -191,6 +200,8 @@ def parse_args(cmd: str, argv: list[str]) -> Options:
         o.output |= 1   # extension: append S, theta_W and the spectrum (print_sfs never prints them)
     if cmd == "sfs" and "--joint" in argv:
         o.output |= 2   # extension: append Fst and the joint spectrum of every population pair
+    if cmd == "sfs" and "--dstat" in argv:
+        o.output |= 4   # extension: append D, f_d, f_dM and their sums of every population triple
     if cmd == "ld" and "e" in present:
         o.min_freq = 2
     if cmd == "snp" and "v" in present:

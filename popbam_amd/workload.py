@@ -218,6 +218,43 @@ class JointSfs:
         return cls(hp.ctx, hp.n_win, outidx, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
+class DStat:
+    """pbg_window_dstat: Patterson's D (ABBA-BABA), f_d and f_dM per window and population triple.
+    `triples` is a list of (p1, p2, p3) population indices (a host array of the call).  Owns the
+    four device arrays -- sums[n_win, n_triples, 6] (int64: ABBA, BABA, FD2, FD3, GD1, GD3) and
+    d, fd, fdm[n_win, n_triples] (float64) -- and runs on a HotPath's rows and windows, or on any
+    rows tensor with a window list.  `outidx` counts only when the context has PBG_F_OUTGROUP."""
+
+    def __init__(self, ctx: _lib.Context, n_win: int, triples, outidx: int = 0, device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        self.triples = [tuple(int(x) for x in t) for t in triples]
+        self.n_triples = len(self.triples)
+        self._arr = (_lib.PbgTriple * max(1, self.n_triples))(*[_lib.PbgTriple(*t) for t in self.triples])
+        self.opts = _lib.PbgDstatOpts(outidx, self.n_triples, C.cast(self._arr, C.POINTER(_lib.PbgTriple)))
+        self.sums = torch.zeros((n_win, self.n_triples, 6), dtype=torch.int64, device=device)
+        self.d = torch.zeros((n_win, self.n_triples), dtype=torch.float64, device=device)
+        self.fd = torch.zeros((n_win, self.n_triples), dtype=torch.float64, device=device)
+        self.fdm = torch.zeros((n_win, self.n_triples), dtype=torch.float64, device=device)
+        self.out = _lib.PbgDstatOut(_ptr(self.sums), _ptr(self.d), _ptr(self.fd), _ptr(self.fdm))
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_dstat(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                             C.byref(self.opts), C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_dstat")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", triples, outidx: int = 0, stream=None) -> "DStat":
+        """The D statistics of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, triples, outidx, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 
