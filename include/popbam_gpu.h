@@ -310,6 +310,49 @@ typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wa
 int pbg_window_dstat(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                      uint32_t n_win, const pbg_dstat_opts *opts, const pbg_dstat_out *out, void *stream);
 
+/* Haplotype frequency spectrum, Garud's H1, H12, H123 and H2/H1 and an unbiased haplotype diversity
+ * per window and population (an extension; nhaps / hap_val of PBG_S_HAP_K stay calc_nhaps' numbers,
+ * local-index quirk and integer n/(n-1) included).  The context has populations 0 .. n_pops-1;
+ * population i has n_i samples and mask pm_i, and its samples in ascending sample id have local
+ * indices 0 .. n_i-1.  The sites of window [beg, end) are its rows with the segregating bit set (the
+ * set pbg_window_jsfs and pbg_window_dstat are taken over); the haplotype of a sample is the sequence
+ * of its bit over those rows, in row order.  Two samples of a population are in the same class iff
+ * their haplotypes are equal at every site of the window; the outgroup flip does not matter and is
+ * not applied.  With the class sizes sorted descending, c_1 >= c_2 >= ... >= c_K (c_2 = c_3 = 0 when
+ * there are fewer classes), Q = sum c_k^2 and N2 = (int64)n_i * n_i, element (w, i) at w * n_pops + i:
+ *   k       int32: K, the number of classes
+ *   counts  int32: c_1 .. c_K, then zeros, at (w * n_pops + i) * stride; stride = pbg_hfs_stride(),
+ *           the largest population size
+ *   cls     uint8 at w * n_samples + s: the local index of the lowest-id sample of s's population
+ *           whose haplotype equals s's; 255 for a sample that is in no population
+ *   sums    four int64: Q, c_1, c_2, c_3
+ *   h       five doubles, from the integers (products in int64) with exactly these IEEE operations
+ *           and no fused multiply-add:
+ *               H1   = (double)Q / (double)N2
+ *               H12  = (double)(Q + 2*c1*c2) / (double)N2
+ *               H123 = (double)(Q + 2*(c1*c2 + c1*c3 + c2*c3)) / (double)N2
+ *               H2H1 = (double)(Q - c1*c1) / (double)Q
+ *               Hd   = (double)(N2 - Q) / (double)(n_i*(n_i-1))     a quiet NaN when n_i < 2
+ * A non-empty window with no segregating row is one class: K = 1, c_1 = n_i, H1 = 1.  A window with
+ * beg >= end gives k = 0, zero counts and sums, cls = 255 and five NaNs.  A window outside
+ * [0, n_rows] is not read: it gives the empty window's outputs and the next pbg_check returns
+ * PBG_E_RANGE.  A NULL member of pbg_hfs_out is skipped.  Asynchronous; no workspace and no plan, so
+ * it is free to interleave with pbg_window_stats, pbg_window_ld_decay, pbg_window_jsfs and
+ * pbg_window_dstat on one stream.  Integer ORs and adds only, so two runs give the same bytes; no
+ * list of sites is kept, so a window of any length works.  PBG_E_ARG for a null ctx, rows, wins or
+ * out and for a context whose pop_n[i] is not the number of samples in pop_mask[i].  A sample that
+ * sits in two populations cannot reach this call: pbg_create refuses overlapping masks. */
+typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int32_t *k;                /* [n_win * n_pops]                    */
+    int32_t *counts;           /* [n_win * n_pops * pbg_hfs_stride()] */
+    uint8_t *cls;              /* [n_win * n_samples]                 */
+    int64_t *sums;             /* [n_win * n_pops * 4]  Q, c1, c2, c3 */
+    double  *h;                /* [n_win * n_pops * 5]  H1, H12, H123, H2H1, Hd */
+} pbg_hfs_out;
+int pbg_hfs_stride(const pbg_ctx *ctx);   /* the largest population size; 0 for a null ctx */
+int pbg_window_hfs(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                   uint32_t n_win, const pbg_hfs_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -362,6 +405,11 @@ typedef struct {
                               appends, per population, "decay[pop]:" the bins' mean r^2 (NA for an
                               empty bin) and "pairs[pop]:" their pair counts, comma-separated, after
                               the reference's columns; they ignore min_snps                      */
+    int32_t  hfs;          /* haplo --hfs (any -o; 0 = off): a streamed run also runs pbg_window_hfs on
+                              the command's windows and appends, per population, "H1[pop]:",
+                              "H12[pop]:", "H123[pop]:", "H2H1[pop]:", "Hd[pop]:" (NA for NaN) and
+                              "hfs[pop]:" the K class sizes, comma-separated, after the reference's
+                              columns; they ignore min_sites                                      */
 } pbg_cmd;
 
 /* Runs `popbam <cmd>` over a HOST pileup batch that covers contig positions
@@ -379,7 +427,7 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
  * prints (+1 applied here).  Same return convention as pbg_run.  It takes no decay arrays and
  * prints the reference's columns only, whatever the command's decay_bin says; no joint-spectrum
  * arrays and no D-statistic arrays either, so sfs output bits 1 (--joint) and 2 (--dstat) add
- * nothing here.                                                                             */
+ * nothing here; no haplotype-spectrum arrays, so haplo's hfs adds nothing here.            */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

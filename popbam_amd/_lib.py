@@ -30,7 +30,8 @@ EXPORTS = ["pbg_create", "pbg_destroy", "pbg_last_error", "pbg_row_bytes", "pbg_
            "pbg_format", "pbg_build_info", "pbg_set_kernel_timing", "pbg_kernel_time", "pbg_call_time", "pbg_synth_max_keys",
            "pbg_synth_pileup", "pbg_stream_open", "pbg_stream_push", "pbg_stream_push_compact", "pbg_stream_finish", "pbg_stream_text",
            "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay",
-           "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs", "pbg_window_dstat"]
+           "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs", "pbg_window_dstat",
+           "pbg_hfs_stride", "pbg_window_hfs"]
 
 PBG_DECAY_MAX_BINS = 256
 PBG_DSTAT_MAX_TRIPLES = 4096
@@ -81,7 +82,8 @@ class PbgCmd(C.Structure):
                 ("min_freq", C.c_int32), ("outidx", C.c_int32), ("jc", C.c_int32), ("windowed", C.c_int32),
                 ("win_size", C.c_int64), ("beg", C.c_int32), ("end", C.c_int32), ("chr_name", C.c_char_p),
                 ("sample_names", C.POINTER(C.c_char_p)), ("pop_names", C.POINTER(C.c_char_p)),
-                ("refid", C.c_char_p), ("ms_windows", C.c_int32), ("decay_bin", C.c_int32), ("decay_bins", C.c_int32)]
+                ("refid", C.c_char_p), ("ms_windows", C.c_int32), ("decay_bin", C.c_int32), ("decay_bins", C.c_int32),
+                ("hfs", C.c_int32)]
 
 
 class PbgDecayOpts(C.Structure):
@@ -110,6 +112,10 @@ class PbgDstatOpts(C.Structure):
 
 class PbgDstatOut(C.Structure):
     _fields_ = [("sums", C.c_void_p), ("d", C.c_void_p), ("fd", C.c_void_p), ("fdm", C.c_void_p)]
+
+
+class PbgHfsOut(C.Structure):
+    _fields_ = [("k", C.c_void_p), ("counts", C.c_void_p), ("cls", C.c_void_p), ("sums", C.c_void_p), ("h", C.c_void_p)]
 
 
 class PbgStreamProf(C.Structure):
@@ -173,6 +179,10 @@ def load(torch_first: bool = True):
     lib.pbg_window_jsfs.restype = C.c_int
     lib.pbg_window_dstat.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgDstatOpts), P(PbgDstatOut), vp]
     lib.pbg_window_dstat.restype = C.c_int
+    lib.pbg_hfs_stride.argtypes = [vp]
+    lib.pbg_hfs_stride.restype = C.c_int
+    lib.pbg_window_hfs.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgHfsOut), vp]
+    lib.pbg_window_hfs.restype = C.c_int
     lib.pbg_build_info.argtypes = []
     lib.pbg_build_info.restype = C.c_char_p
     lib.pbg_check.argtypes = [vp, vp]

@@ -86,7 +86,7 @@ std::vector<int32_t> jsfs_offsets(const pbg::DevParams &dp) {
 }  // namespace
 
 namespace pbg {
-extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat;
+extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat, kBuildKind_hfs;
 }
 
 namespace {
@@ -113,6 +113,7 @@ const char *pbg_last_error(const pbg_ctx *ctx) { return ctx ? ctx->err.c_str() :
 int pbg_row_bytes(const pbg_ctx *ctx) { return ctx ? ctx->row_bytes : 0; }
 int pbg_k_bytes(const pbg_ctx *ctx) { return ctx ? (ctx->dp.k16 ? 2 : 1) : 0; }
 int pbg_sfs_stride(const pbg_ctx *ctx) { return ctx ? ctx->dp.sfs_stride : 0; }
+int pbg_hfs_stride(const pbg_ctx *ctx) { return ctx ? ctx->dp.pop_nmax : 0; }
 
 int pbg_create(pbg_ctx **out, int device, const pbg_params *p) {
     if (!out || !p) return fail(nullptr, PBG_E_ARG, "null argument");
@@ -467,7 +468,7 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 
 const char *pbg_build_info(void) {
     const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay,
-                               pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat});
+                               pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat, pbg::kBuildKind_hfs});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -840,6 +841,29 @@ int pbg_window_dstat(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
     A.fd = out->fd;
     A.fdm = out->fdm;
     HIPCHK(c, pbg::launch_window_dstat(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    return PBG_OK;
+}
+
+int pbg_window_hfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                   const pbg_hfs_out *out, void *stream) {
+    if (!c || !rows || !wins || !out) return fail(c, PBG_E_ARG, "null argument");
+    // a class label is a rank inside pop_mask and the doubles divide by pop_n: they must agree.  (A sample
+    // in two populations cannot get here: pbg_create refuses overlapping masks.)
+    for (int i = 0; i < c->dp.npops; ++i)
+        if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
+            return fail(c, PBG_E_ARG, "hfs: pop_n must be the number of samples in pop_mask");
+    if (n_win == 0) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    pbg::HfsArgs A{};
+    A.wins = wins;
+    A.err = c->d_err;
+    A.k = out->k;
+    A.counts = out->counts;
+    A.cls = out->cls;
+    A.sums = out->sums;
+    A.h = out->h;
+    HIPCHK(c, pbg::launch_window_hfs(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
     return PBG_OK;
 }
 

@@ -413,6 +413,23 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                         if (ok) o.i(w.hap_min[k]); else o.na();
                     }
             }
+            // --hfs: per population Garud's H statistics, the haplotype diversity and the class sizes,
+            // after the reference's columns (the default output is unchanged); not subject to -k
+            if (c.hfs && w.hfs_h.size() == (size_t)np * 5 && (int)w.hfs_k.size() == np &&
+                w.hfs_counts.size() == (size_t)np * w.hfs_stride)
+                for (int i = 0; i < np; i++) {
+                    const std::string lab = "[" + pn(c, i) + "]:\t";
+                    static const char *const nm[5] = {"\tH1", "\tH12", "\tH123", "\tH2H1", "\tHd"};
+                    for (int k = 0; k < 5; k++) {
+                        o.t(nm[k] + lab);
+                        if (std::isnan(w.hfs_h[(size_t)i * 5 + k])) o.na(); else o.f(w.hfs_h[(size_t)i * 5 + k]);
+                    }
+                    o.t("\thfs" + lab);
+                    for (int k = 0; k < w.hfs_k[i] && k < w.hfs_stride; k++) {
+                        if (k) o.t(",");
+                        o.i(w.hfs_counts[(size_t)i * w.hfs_stride + k]);
+                    }
+                }
             break;
         case PBG_CMD_TREE:
             format_nj(o, c, n, w);

@@ -376,6 +376,21 @@ struct DstatArgs {
     double *d, *fd, *fdm;      // [n_win * n_triples] each, or null
 };
 
+// window_hfs_kernel (pbg_window_hfs): class sizes of equal haplotypes, Garud's H statistics and the
+// haplotype diversity per (window, population).  Every sample's difference mask, the class-size
+// histogram and its sorted copy live in LDS, one slot per sample (populations are disjoint, so the
+// slots of population i are [pop_start[i], pop_start[i + 1])).
+constexpr int kHfsSlots = 128;           // PBG_MAX_SAMPLES rounded up
+struct HfsArgs {
+    const pbg_window *wins;
+    int *err;
+    int32_t *k;                // [n_win * npops] or null
+    int32_t *counts;           // [n_win * npops * pop_nmax] or null
+    uint8_t *cls;              // [n_win * n] or null
+    int64_t *sums;             // [n_win * npops * 4] or null
+    double *h;                 // [n_win * npops * 5] or null
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -518,5 +533,8 @@ hipError_t launch_window_jsfs(int row_bytes, const DevParams &P, const void *row
 // dstat_kernel.hip (dynamic LDS: min(A.n_triples, kDstatLdsTriples) * 48 bytes)
 hipError_t launch_window_dstat(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                                const DstatArgs &A, hipStream_t stream);
+// hfs_kernel.hip (static LDS only)
+hipError_t launch_window_hfs(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                             const HfsArgs &A, hipStream_t stream);
 
 }  // namespace pbg

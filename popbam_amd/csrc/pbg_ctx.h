@@ -52,6 +52,8 @@ struct StreamBufs {
     size_t jsfs_cap = 0;
     void *d_dstat = nullptr;             // sfs --dstat: sums | d | fd | fdm of one block of windows
     size_t dstat_cap = 0;
+    void *d_hfs = nullptr;               // haplo --hfs: h | counts | k of one block of windows
+    size_t hfs_cap = 0;
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };

@@ -45,6 +45,12 @@ struct WindowHost {
     // [t * 6] (pbg_window_dstat over dstat_triples(np)); empty when the caller has none (pbg_format)
     std::vector<double> dstat_d, dstat_fd, dstat_fdm;
     std::vector<int64_t> dstat_sums;
+    // haplo --hfs (pbg_cmd.hfs): H1, H12, H123, H2H1, Hd of population p at [p * 5], its class count
+    // at hfs_k[p] and its sorted class sizes at [p * hfs_stride] (pbg_window_hfs); empty when the
+    // caller has none (pbg_format)
+    std::vector<double> hfs_h;
+    std::vector<int32_t> hfs_k, hfs_counts;
+    int hfs_stride = 0;
 };
 
 // sfs --dstat's triples of n_pops populations: all (i, j, k) with i < j and k neither, in

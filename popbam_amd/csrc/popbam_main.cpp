@@ -99,6 +99,7 @@ struct Options {
     unsigned char min_mapQ = 13, min_baseQ = 13;
     int min_sites = 10, output = 0, min_snps = 10, min_freq = 1;          // <cmd>Data constructors
     int decay_bin = 0, decay_bins = 0;                                    // ld --decay=BIN,NBINS (0: off)
+    int hfs = 0;                                                          // haplo --hfs (0: off)
     unsigned int win_size = 0;
     long double het_prior = 0.0001L;                                      // -z: parsed, unused
 };
@@ -286,6 +287,8 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
         o.output |= 2;   // extension: Fst and the joint spectrum of every population pair after those
     if (cmd == "sfs" && std::find(argv.begin(), argv.end(), std::string("--dstat")) != argv.end())
         o.output |= 4;   // extension: D, f_d, f_dM and their sums of every population triple after those
+    if (cmd == "haplo" && std::find(argv.begin(), argv.end(), std::string("--hfs")) != argv.end())
+        o.hfs = 1;   // extension: H1, H12, H123, H2H1, Hd and the class sizes of every population (any -o)
     if (cmd == "ld" && tk.present('e')) o.min_freq = 2;
     if (cmd == "snp" && tk.present('v')) o.flag |= BAM_VARIANT;
     if (cmd == "snp" && tk.present('z')) o.flag |= BAM_HETEROZYGOTE;
@@ -767,6 +770,7 @@ std::string run(const std::string &cmd, const std::vector<std::string> &argv, in
         c.ms_windows = (blocks.size() > 1 || world > 1) ? (int32_t)(bi == 0 ? ms0 : -1) : 0;
         c.decay_bin = o.decay_bin;
         c.decay_bins = o.decay_bins;
+        c.hfs = o.hfs;
         t0 = Clock::now();
         pbf_kstream *ks = nullptr;
         if (pbf_kstream_open(o.bamfile.c_str(), std::max(1, threads), piece, tid, (int32_t)lo, (int32_t)hi,

@@ -466,6 +466,43 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         k1 = first + cnt;
         return PBG_OK;
     };
+    // haplo --hfs: the haplotype-spectrum kernel over the same windows (its columns follow the
+    // reference's), in blocks of windows of at most kHfsStage bytes
+    const bool hfs = cmd->cmd == PBG_CMD_HAPLO && cmd->hfs != 0;
+    const size_t hS = (size_t)pbg_hfs_stride(c), hper = (size_t)np * (hS * 4 + 4 + 40);   // bytes per window
+    constexpr size_t kHfsStage = 64u << 20;
+    const uint32_t hblock = hfs ? (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kHfsStage / hper)) : 0;
+    std::vector<double> h_hh;
+    std::vector<int32_t> h_hcounts, h_hk;
+    uint32_t m0 = 0, m1 = 0;   // the windows of the block on the host
+    auto hfs_block = [&](uint32_t first) -> int {
+        const uint32_t cnt = std::min(hblock, nw - first);
+        const size_t per = (size_t)hblock * np, need_h = per * (hS * 4 + 4 + 40);
+        if (c->sb.hfs_cap < need_h) {
+            if (c->sb.d_hfs) HIPCHK(c, hipFree(c->sb.d_hfs));
+            c->sb.d_hfs = nullptr;
+            c->sb.hfs_cap = 0;
+            HIPCHK(c, hipMalloc(&c->sb.d_hfs, need_h));
+            c->sb.hfs_cap = need_h;
+        }
+        double *d_h = (double *)c->sb.d_hfs;
+        int32_t *d_counts = (int32_t *)(d_h + per * 5), *d_k = d_counts + per * hS;
+        const pbg_hfs_out hout{d_k, d_counts, nullptr, nullptr, d_h};
+        int hrc = pbg_window_hfs(c, d_rows, dsites, d_win + first, cnt, &hout, s);
+        if (hrc) return hrc;
+        if ((hrc = pbg_check(c, s))) return hrc;
+        const size_t got = (size_t)cnt * np;
+        h_hh.resize(got * 5);
+        h_hcounts.resize(got * hS);
+        h_hk.resize(got);
+        HIPCHK(c, d2h(h_hh.data(), d_h, got * 40));
+        HIPCHK(c, d2h(h_hcounts.data(), d_counts, got * hS * 4));
+        HIPCHK(c, d2h(h_hk.data(), d_k, got * 4));
+        HIPCHK(c, hipStreamSynchronize(s));
+        m0 = first;
+        m1 = first + cnt;
+        return PBG_OK;
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
@@ -484,6 +521,13 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             wh.dstat_d = slice(h_dd, (size_t)(i - k0) * dT, dT);
             wh.dstat_fd = slice(h_dfd, (size_t)(i - k0) * dT, dT);
             wh.dstat_fdm = slice(h_dfdm, (size_t)(i - k0) * dT, dT);
+        }
+        if (hfs) {
+            if (i >= m1 && (rc = hfs_block(i))) return rc;
+            wh.hfs_h = slice(h_hh, (size_t)(i - m0) * np * 5, (size_t)np * 5);
+            wh.hfs_counts = slice(h_hcounts, (size_t)(i - m0) * np * hS, (size_t)np * hS);
+            wh.hfs_k = slice(h_hk, (size_t)(i - m0) * np, np);
+            wh.hfs_stride = (int)hS;
         }
         wh.beg = win[i].first;
         wh.end = win[i].second;
@@ -531,7 +575,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay, b.d_jsfs, b.d_dstat})
+    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay, b.d_jsfs, b.d_dstat, b.d_hfs})
         if (p) (void)hipFree(p);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

@@ -77,6 +77,7 @@ class _Cmd:
         c.refid = self._refid
         c.ms_windows = ms_windows
         c.decay_bin, c.decay_bins = o.decay_bin, o.decay_bins
+        c.hfs = o.hfs
         self.c = c
 
 

@@ -255,6 +255,45 @@ class DStat:
         return cls(hp.ctx, hp.n_win, triples, outidx, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
+class Hfs:
+    """pbg_window_hfs: the haplotype frequency spectrum, Garud's H statistics and the haplotype
+    diversity per window and population.  Owns the five device arrays -- k[n_win, n_pops] (int32),
+    counts[n_win, n_pops, stride] (int32, sorted descending, stride = the largest population),
+    cls[n_win, n_samples] (uint8), sums[n_win, n_pops, 4] (int64: Q, c1, c2, c3) and
+    h[n_win, n_pops, 5] (float64: H1, H12, H123, H2H1, Hd) -- and runs on a HotPath's rows and
+    windows, or on any rows tensor with a window list."""
+
+    NAMES = ("k", "counts", "cls", "sums", "h")
+
+    def __init__(self, ctx: _lib.Context, n_win: int, device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        n, np_ = ctx.params.n_samples, ctx.params.n_pops
+        self.stride = int(ctx.lib.pbg_hfs_stride(ctx.h))
+        self.k = torch.zeros((n_win, np_), dtype=torch.int32, device=device)
+        self.counts = torch.zeros((n_win, np_, self.stride), dtype=torch.int32, device=device)
+        self.cls = torch.zeros((n_win, n), dtype=torch.uint8, device=device)
+        self.sums = torch.zeros((n_win, np_, 4), dtype=torch.int64, device=device)
+        self.h = torch.zeros((n_win, np_, 5), dtype=torch.float64, device=device)
+        self.out = _lib.PbgHfsOut(*(_ptr(getattr(self, k)) for k in self.NAMES))
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_hfs(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                           C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_hfs")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", stream=None) -> "Hfs":
+        """The haplotype spectrum of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 

@@ -1,0 +1,753 @@
+"""`haplo --hfs`: the haplotype frequency spectrum, Garud's H1, H12, H123, H2/H1 and the haplotype
+diversity per window and population (pbg_window_hfs, include/popbam_gpu.h; DESIGN.md "Haplotype
+frequency spectrum").  The reference has no such output, so the checker lives here: `ref_hfs` restates
+the header's definition -- a sample's haplotype is the tuple of its bits over the window's segregating
+rows, equal tuples are one class, the sizes go through sorted(reverse=True), Q and the products are
+Python integers and the five doubles are the header's IEEE operations on Python floats.  Every
+comparison is exact: equal integers, equal bits for doubles, isnan where the checker has NaN."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import fixtures
+import harness
+from popbam_amd import cli
+from popbam_amd import options as opt
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(REPO, "bin", "popbam")
+BOUNDS_LIB = os.path.join(REPO, "popbam_amd", "variants", "bounds", "libpopbam_gpu.so")
+SEED = 0x4F5
+COUNTED, SEG = 2, 4   # harness flags bits
+NAMES = ("k", "counts", "cls", "sums", "h")
+HNAMES = ("H1", "H12", "H123", "H2H1", "Hd")
+
+
+# ---- the checker -----------------------------------------------------------------------
+def sample_bits(types, n):
+    """types ([L] u64, or [L, 2] for n > 64) -> [L, n] uint8, column s = the bit of sample s."""
+    t = np.asarray(types, dtype=np.uint64)
+    if t.ndim == 1:
+        t = np.stack([t, np.zeros(len(t), np.uint64)], axis=1)
+    b = np.unpackbits(np.ascontiguousarray(t).view(np.uint8).reshape(len(t), 16), axis=1, bitorder="little")
+    return b[:, :n]
+
+
+def members_of(mask, n):
+    return [s for s in range(n) if (mask >> s) & 1]
+
+
+def _div(a, b):
+    """(double)a / (double)b; the header's 0 / 0 (an empty population) is IEEE's NaN."""
+    return float("nan") if b == 0 else float(a) / float(b)
+
+
+def h_of(sizes, n_i):
+    """(Q, c1, c2, c3) and the five doubles from the sorted class sizes, operation by operation."""
+    c = list(sizes) + [0, 0, 0]
+    c1, c2, c3 = c[0], c[1], c[2]
+    q = sum(x * x for x in sizes)
+    n2 = n_i * n_i
+    h = (_div(q, n2), _div(q + 2 * c1 * c2, n2), _div(q + 2 * (c1 * c2 + c1 * c3 + c2 * c3), n2), _div(q - c1 * c1, q),
+         float("nan") if n_i < 2 else float(n2 - q) / float(n_i * (n_i - 1)))
+    return (q, c1, c2, c3), h
+
+
+def ref_hfs(types, flags, pop_masks, pop_n, n, wins):
+    """k[nw, np] i32, counts[nw, np, stride] i32, cls[nw, n] u8, sums[nw, np, 4] i64, h[nw, np, 5] f64.
+    A window with beg >= end, or outside the rows, is the empty window."""
+    bits_ = sample_bits(types, n)
+    seg = (np.asarray(flags) & SEG) > 0
+    L, nw, npop = len(seg), len(wins), len(pop_masks)
+    stride = max(pop_n)
+    k = np.zeros((nw, npop), np.int32)
+    counts = np.zeros((nw, npop, stride), np.int32)
+    cls = np.full((nw, n), 255, np.uint8)
+    sums = np.zeros((nw, npop, 4), np.int64)
+    h = np.full((nw, npop, 5), np.nan, np.float64)
+    for w, (beg, end) in enumerate(wins):
+        if beg >= end or beg < 0 or end > L:
+            continue
+        sub = bits_[beg + np.flatnonzero(seg[beg:end])]
+        for i, (pm, n_i) in enumerate(zip(pop_masks, pop_n)):
+            first, size = {}, {}
+            for local, s in enumerate(members_of(pm, n)):
+                hap = tuple(sub[:, s].tolist())
+                first.setdefault(hap, local)
+                size[hap] = size.get(hap, 0) + 1
+                cls[w, s] = first[hap]
+            sizes = sorted(size.values(), reverse=True)
+            k[w, i] = len(sizes)
+            counts[w, i, :len(sizes)] = sizes
+            sums[w, i], h[w, i] = h_of(sizes, n_i)
+    return k, counts, cls, sums, h
+
+
+def brute_classes(types, flags, members, n, beg, end):
+    """O(n^2 S): sample pairs compared site by site; the classes as sorted sizes and per-member labels."""
+    bits_ = sample_bits(types, n)
+    rows = [r for r in range(beg, end) if flags[r] & SEG]
+    label = []
+    for a, s in enumerate(members):
+        lab = a
+        for b in range(a):
+            if all(bits_[r, s] == bits_[r, members[b]] for r in rows):
+                lab = b
+                break
+        label.append(lab)
+    return sorted((label.count(x) for x in set(label)), reverse=True), label
+
+
+def bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+def _assert_same(got, want, what=""):
+    for g, w, nm in zip(got, want, NAMES):
+        assert g.shape == w.shape and g.dtype == w.dtype, (what, nm, g.shape, w.shape, g.dtype, w.dtype)
+        if g.dtype == np.float64:
+            same = np.where(np.isnan(w), np.isnan(g), bits(g) == bits(w))
+        else:
+            same = g == w
+        assert same.all(), (what, nm, np.argwhere(~same)[:5].tolist(), g[~same][:5], w[~same][:5])
+
+
+def _random_types(rng, L, n):
+    if n <= 64:
+        return rng.integers(0, 1 << n, L, dtype=np.uint64)
+    t = np.zeros((L, 2), np.uint64)
+    t[:, 0] = rng.integers(0, 1 << 64, L, dtype=np.uint64)
+    t[:, 1] = rng.integers(0, 1 << (n - 64), L, dtype=np.uint64)
+    return t
+
+
+def _founder_types(rng, L, n, founders):
+    """Rows in which every sample copies one of a few founders (the copy changes every 64 rows), so that
+    windows hold classes of several samples."""
+    out = np.zeros((L, 2), np.uint64)
+    for r0 in range(0, L, 64):
+        src = rng.integers(0, founders, n)
+        fb = rng.integers(0, 2, (min(64, L - r0), founders))
+        sb = fb[:, src]   # [rows, n]
+        for s in range(n):
+            out[r0:r0 + len(sb), s >> 6] |= sb[:, s].astype(np.uint64) << np.uint64(s & 63)
+    return out if n > 64 else out[:, 0].copy()
+
+
+def _blocks(sizes):
+    """Contiguous population masks of the given sizes."""
+    masks, at = [], 0
+    for s in sizes:
+        masks.append(((1 << s) - 1) << at)
+        at += s
+    return masks
+
+
+# ---- CPU tests ---------------------------------------------------------------------------
+def test_checker_on_a_hand_made_window():
+    """Two populations, samples 0..3 and 4..6, sample 7 in neither.  Rows (bit s = sample s):
+      00010011  samples 0, 1 | 4
+      00100011  samples 0, 1 | 5
+      11111111  not segregating: ignored although it would change nothing
+      10000100  sample 2 | none (sample 7 is in no population)
+    Window [0, 4): population 0 haplotypes 0: 110, 1: 110, 2: 001, 3: 000 -> classes {0, 1}, {2}, {3}:
+    sizes 2, 1, 1, Q = 6, N2 = 16: H1 = 6/16, H12 = (6 + 4)/16, H123 = (6 + 2 (2 + 2 + 1))/16 = 1,
+    H2H1 = (6 - 4)/6, Hd = (16 - 6)/12.  Population 1: 4: 100, 5: 010, 6: 000: three singletons, Q = 3,
+    N2 = 9: H1 = 3/9, H12 = 5/9, H123 = 1, H2H1 = 2/3, Hd = 6/6.
+    Window [2, 3) has no segregating row: one class each.  Window (1, 1) is empty."""
+    types = np.array([0b00010011, 0b00100011, 0b11111111, 0b10000100], np.uint64)
+    flags = np.array([COUNTED | SEG, COUNTED | SEG, COUNTED, COUNTED | SEG], np.uint8)
+    masks, pop_n = [0b00001111, 0b01110000], [4, 3]
+    k, counts, cls, sums, h = ref_hfs(types, flags, masks, pop_n, 8, [(0, 4), (2, 3), (1, 1)])
+    assert k.tolist() == [[3, 3], [1, 1], [0, 0]]
+    assert counts.tolist() == [[[2, 1, 1, 0], [1, 1, 1, 0]], [[4, 0, 0, 0], [3, 0, 0, 0]], [[0] * 4, [0] * 4]]
+    assert cls.tolist() == [[0, 0, 2, 3, 0, 1, 2, 255], [0, 0, 0, 0, 0, 0, 0, 255], [255] * 8]
+    assert sums.tolist() == [[[6, 2, 1, 1], [3, 1, 1, 1]], [[16, 4, 0, 0], [9, 3, 0, 0]], [[0] * 4, [0] * 4]]
+    assert h[0, 0].tolist() == [6 / 16, 10 / 16, 1.0, 2 / 6, 10 / 12]
+    assert h[0, 1].tolist() == [3 / 9, 5 / 9, 1.0, 2 / 3, 1.0]
+    assert h[1].tolist() == [[1.0, 1.0, 1.0, 0.0, 0.0]] * 2
+    assert np.isnan(h[2]).all()
+    # a population of one: Hd is NaN, the rest is the single class
+    k1, _, cls1, sums1, h1 = ref_hfs(types, flags, [0b1], [1], 8, [(0, 4)])
+    assert (k1[0, 0], sums1[0, 0].tolist(), cls1[0].tolist()) == (1, [1, 1, 0, 0], [0] + [255] * 7)
+    assert h1[0, 0, :4].tolist() == [1.0, 1.0, 1.0, 0.0] and np.isnan(h1[0, 0, 4])
+
+
+@pytest.mark.parametrize("n,sizes", [(7, [3, 4]), (13, [6, 1, 5]), (70, [40, 30])])
+def test_checker_agrees_with_pairwise_comparison(n, sizes):
+    """Random small matrices: the tuple grouping against an O(n^2 S) comparison of every sample pair."""
+    rng = np.random.default_rng(n)
+    L = 60
+    types = _founder_types(rng, L, n, 3)
+    flags = np.where(rng.random(L) < 0.4, COUNTED | SEG, COUNTED).astype(np.uint8)
+    masks = _blocks(sizes)
+    wins = [(0, L), (0, 1), (5, 9), (20, 50), (59, 60)]
+    k, counts, cls, sums, h = ref_hfs(types, flags, masks, sizes, n, wins)
+    seen = set()
+    for w, (beg, end) in enumerate(wins):
+        for i, pm in enumerate(masks):
+            mem = members_of(pm, n)
+            want, label = brute_classes(types, flags, mem, n, beg, end)
+            assert counts[w, i, :len(want)].tolist() == want and not counts[w, i, len(want):].any()
+            assert k[w, i] == len(want) and cls[w, mem].tolist() == label
+            assert sums[w, i].tolist() == [sum(x * x for x in want)] + (want + [0, 0])[:3]
+            seen.add(len(want))
+    assert len(seen) >= 2   # more than one class count came up
+
+
+def test_hfs_option_parses():
+    base = ["-f", "ref.fa", "-w", "10"]
+    for o_args, want in (([], 0), (["-o", "0"], 0), (["-o", "1"], 1), (["-o", "2"], 2)):
+        plain = opt.parse_args("haplo", base + o_args + ["in.bam", "chr1:1-500"])
+        assert (plain.hfs, plain.output) == (0, want)
+        for argv in (base + o_args + ["--hfs", "in.bam", "chr1:1-500"], ["--hfs"] + base + o_args + ["in.bam", "chr1:1-500"],
+                     base + o_args + ["in.bam", "--hfs", "chr1:1-500"], base + o_args + ["in.bam", "chr1:1-500", "--hfs"]):
+            o = opt.parse_args("haplo", argv)
+            assert o.hfs == 1
+            o.hfs = 0
+            assert o == plain   # every other field as without the token
+    # only haplo has it
+    for cmd in ("nucdiv", "sfs", "ld", "diverge", "snp", "tree"):
+        assert opt.parse_args(cmd, base + ["--hfs", "in.bam", "chr1"]).hfs == 0
+    with pytest.raises(opt.PopbamError, match="Not a valid output option"):
+        opt.parse_args("haplo", base + ["-o", "3", "--hfs", "in.bam", "chr1"])
+
+
+def _oracle_text(params, types, flags, cmd_id, output, windows):
+    p = harness.oracle_params_from(params)
+    c = harness.OrcCmd()
+    n, np_ = params.n_samples, params.n_pops
+    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq, c.jc = cmd_id, output, 0, 10, 1, 0
+    c.chr_name = b"chr1"
+    sn = (C.c_char_p * n)(*[f"s{i}".encode() for i in range(n)])
+    pn = (C.c_char_p * np_)(*[f"p{i}".encode() for i in range(np_)])
+    c.sample_names = C.cast(sn, C.POINTER(C.c_char_p))
+    c.pop_names = C.cast(pn, C.POINTER(C.c_char_p))
+    c.refid = b"ref"
+    wb = np.array([a for a, _ in windows], np.int32)
+    we = np.array([b for _, b in windows], np.int32)
+    cap = 1 << 22
+    buf = C.create_string_buffer(cap)
+    r = harness.oracle().orc_windows_from_sites(C.byref(p), C.byref(c), types.ctypes.data, flags.ctypes.data,
+                                                len(windows), wb.ctypes.data, we.ctypes.data, buf, cap)
+    assert r >= 0
+    return buf.value.decode()
+
+
+def _one_population(n):
+    from popbam_amd import workload
+    return workload.default_params(n, 1)
+
+
+CROSS = [(12, 3), (40, 4), (96, 5)]   # (samples, founders)
+CROSS_L = 3000
+CROSS_WINS = [(0, CROSS_L), (0, 64), (64, 128), (100, 140), (1000, 1010), (2000, 2900), (7, 8)]
+
+
+def _cross_rows(n, founders):
+    rng = np.random.default_rng(100 + n)
+    types = _founder_types(rng, CROSS_L, n, founders)
+    flags = np.where(rng.random(CROSS_L) < 0.05, COUNTED | SEG, COUNTED).astype(np.uint8)
+    return types, flags
+
+
+@pytest.mark.parametrize("n,founders", CROSS, ids=[f"n{a}" for a, _ in CROSS])
+def test_one_population_agrees_with_the_oracles_calc_nhaps(n, founders):
+    """One population that holds samples 0 .. n-1, n > 2, fewer than 65,536 segregating rows in a window:
+    calc_nhaps' local indices are the sample ids, its n/(n-1) is 1 and its u16 difference counts cannot
+    wrap to zero, so K[pop] of the CPU oracle's `haplo -o 0` is the checker's k and Kdiv[pop] prints
+    1.0 - Q/(n*n) (the GPU test below compares the bits)."""
+    types, flags = _cross_rows(n, founders)
+    params = _one_population(n)
+    k, counts, cls, sums, h = ref_hfs(types, flags, [params.get_pop_mask(0)], [n], n, CROSS_WINS)
+    lines = _oracle_text(params, types, flags, 1, 0, CROSS_WINS).splitlines()
+    assert len(lines) == len(CROSS_WINS)
+    for w, ln in enumerate(lines):
+        f = ln.split("\t")
+        assert f[4:] == ["K[p0]:", str(k[w, 0]), "Kdiv[p0]:", "%.5f" % (1.0 - float(sums[w, 0, 0]) / float(n * n))], (w, f)
+    assert len(set(k[:, 0].tolist())) > 2 and k.max() > 3
+
+
+# ---- GPU tests ---------------------------------------------------------------------------
+N_SITES = 32_000
+SHAPES = {   # name -> (samples, population masks)
+    "n12p2": (12, _blocks([6, 6])),                                   # 2-byte rows, G = 16
+    "n24p3": (24, _blocks([8, 8, 8])),                                # 4-byte rows
+    "n40p2i": (40, [sum(1 << s for s in range(0, 40, 2)), sum(1 << s for s in range(1, 40, 2))]),   # 8-byte rows
+    "n96p4": (96, _blocks([24] * 4)),                                 # 16-byte rows, two samples per lane
+    "n126p3": (126, _blocks([70, 50, 6])),                            # population 0 straddles the words
+    "n14one": (14, [0b00000000111111, 0b00000001000000, 0b11111100000000]),   # a population of one; sample 7 in none
+}
+_shapes = {}
+
+
+def _params(n, masks, flag=0):
+    from popbam_amd import workload
+    params = workload.default_params(n, len(masks), flag=flag)
+    for i, m in enumerate(masks):
+        params.set_pop_mask(i, m)
+        params.pop_n[i] = bin(m).count("1")
+    return params
+
+
+def _shape(name):
+    """One called synthetic batch per shape, shared by the tests (read only)."""
+    if name not in _shapes:
+        import torch
+        from popbam_amd import _lib, workload
+        n, masks = SHAPES[name]
+        params = _params(n, masks)
+        ctx = _lib.Context(params, 0)
+        syn = workload.SynthPileup(ctx, N_SITES, 10, SEED + n)
+        hp = workload.HotPath(ctx, syn, [(0, N_SITES)], _lib.PBG_S_SFS)
+        hp.call()
+        ctx.sync_check()
+        torch.cuda.synchronize()
+        types, flags = harness.rows_to_sites(hp.rows.cpu().numpy(), ctx.row_bytes, N_SITES, n)
+        _shapes[name] = (ctx, params, hp.rows, types, flags)
+    return _shapes[name]
+
+
+def _windows(n_sites):
+    """A few dozen windows from 3 positions to the whole batch: short ones hold classes of several
+    samples, long ones only singletons."""
+    rng = np.random.default_rng(7)
+    wins = [(0, n_sites), (0, 10_000), (9_999, 20_001), (5, 5), (0, 1)]
+    for ln in (3, 10, 30, 60, 100, 150, 300, 1000, 3000):
+        for s in rng.integers(0, n_sites - ln, 3):
+            wins.append((int(s), int(s) + ln))
+    return wins
+
+
+def _wins_tensor(wins):
+    import torch
+    return torch.tensor([x for ab in wins for x in ab], dtype=torch.int32).reshape(-1, 2).cuda()
+
+
+def _arrays(x):
+    return tuple(getattr(x, k).cpu().numpy().copy() for k in NAMES)
+
+
+def _run_hfs(ctx, rows, n_rows, wins):
+    from popbam_amd import workload
+    j = workload.Hfs(ctx, len(wins))
+    j(rows, _wins_tensor(wins), n_rows)
+    ctx.sync_check()
+    return _arrays(j)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_hfs_matches_the_checker_on_called_rows(gpu_lib, name):
+    ctx, params, rows, types, flags = _shape(name)
+    n, masks = SHAPES[name]
+    pop_n = [bin(m).count("1") for m in masks]
+    wins = _windows(N_SITES)
+    got = _run_hfs(ctx, rows, N_SITES, wins)
+    want = ref_hfs(types, flags, masks, pop_n, n, wins)
+    _assert_same(got, want, name)
+    assert got[1].shape == (len(wins), len(masks), max(pop_n)) and ctx.lib.pbg_hfs_stride(ctx.h) == max(pop_n)
+    big = [i for i, c in enumerate(pop_n) if c > 2]
+    assert (got[0][:, big] == 1).any() and (got[0][:, big] > 3).any() and (got[1][:, big, 1] > 1).any()
+    if name == "n14one":
+        assert np.isnan(got[4][:, 1, 4]).all() and (got[0][[0, 1, 2], 1] == 1).all() and (got[2][:, 7] == 255).all()
+        assert (got[2][[0, 1, 2], 6] == 0).all()
+
+
+def _crafted(n, masks, types, flags):
+    """A context with the given population masks and device rows packed from (types, flags)."""
+    import torch
+    from popbam_amd import _lib
+    params = _params(n, masks)
+    ctx = _lib.Context(params, 0)
+    rows = torch.from_numpy(harness.rows_from_oracle(types, flags, ctx.row_bytes).copy()).cuda()
+    return ctx, params, rows
+
+
+def _scenario_rows():
+    """12 samples, populations 0..5 and 6..11 (2-byte rows: 8 rows per 16-byte word, 2,048 rows per
+    workgroup pass).  Rows are counted and not segregating unless set here."""
+    L = 7000
+    types = np.zeros(L, np.uint64)
+    flags = np.full(L, COUNTED, np.uint8)
+    wins = {}
+
+    def seg(r, t):
+        types[r], flags[r] = t, COUNTED | SEG
+
+    for r in range(0, 100):   # every sample identical at every site
+        seg(r, 0xFFF if r % 3 else 0)
+    wins["identical"] = (0, 100)
+    for s in range(12):       # every sample its own row
+        seg(110 + s, 1 << s)
+    wins["distinct"] = (103, 150)
+    # samples 0 and 1 differ only at the window's first row; rows beg - 1 and end would split more
+    seg(202, 1 << 2)
+    seg(203, 0b000001)
+    seg(250, 0b000011)
+    types[260], types[261] = 0b101010101010, 0xFFF   # sample bits without the segregating bit: ignored
+    seg(291, 1 << 3)
+    wins["first"] = (203, 291)
+    # samples 6 and 7 differ only at the window's last row
+    seg(308, 1 << 8)
+    seg(350, 0b11 << 6)
+    seg(396, 1 << 6)
+    seg(397, 1 << 9)
+    wins["last"] = (309, 397)
+    # ties among the sizes, K > 3: 2, 2, 1, 1 in population 0; 3, 3 in population 1 (K < 3)
+    seg(500, 0b000011)
+    seg(501, 0b001100)
+    seg(502, 0b010000)
+    seg(503, 0b111 << 6)
+    wins["ties"] = (497, 511)
+    wins["noseg"] = (700, 800)
+    wins["empty"] = (50, 50)
+    wins["reversed"] = (60, 40)
+    # longer than one pass: word c of the window goes to wave ((c - c0) / 64) % 4; the only rows that
+    # tell samples apart sit in different waves' slices and in different passes
+    beg = 1003
+    c0 = beg // 8
+
+    def row_of(wave, pass_, off=5):
+        return (c0 + pass_ * 256 + wave * 64 + 17) * 8 + off
+
+    for r in range(beg, 6900, 7):
+        seg(r, 0xFFF if r % 2 else 0)
+    marks = {0: row_of(0, 0), 2: row_of(1, 0), 4: row_of(2, 1), 6: row_of(3, 0), 8: row_of(0, 2), 9: row_of(3, 2)}
+    for s, r in marks.items():
+        assert beg <= r < 6900
+        seg(r, 1 << s)
+    wins["long"] = (beg, 6900)
+    return types, flags, wins, marks
+
+
+@pytest.mark.gpu
+def test_hfs_crafted_rows(gpu_lib):
+    """The scenarios of _scenario_rows against the checker and against the sizes they were built for."""
+    types, flags, named, marks = _scenario_rows()
+    masks, pop_n = _blocks([6, 6]), [6, 6]
+    ctx, params, rows = _crafted(12, masks, types, flags)
+    order = list(named)
+    wins = [named[k] for k in order]
+    got = _run_hfs(ctx, rows, len(types), wins)
+    _assert_same(got, ref_hfs(types, flags, masks, pop_n, 12, wins))
+    k, counts, cls, sums, h = got
+    at = {nm: i for i, nm in enumerate(order)}
+
+    def sizes(nm, i):
+        return counts[at[nm], i][:k[at[nm], i]].tolist()
+
+    assert sizes("identical", 0) == [6] == sizes("identical", 1) and h[at["identical"], :, 0].tolist() == [1.0, 1.0]
+    assert sizes("distinct", 0) == [1] * 6 == sizes("distinct", 1) and cls[at["distinct"]].tolist() == list(range(6)) * 2
+    assert h[at["distinct"], 0].tolist() == [6 / 36, 8 / 36, 12 / 36, 5 / 6, 1.0]
+    assert sizes("first", 0) == [4, 1, 1] and sizes("first", 1) == [6]
+    assert cls[at["first"]].tolist() == [0, 1, 2, 2, 2, 2] + [0] * 6
+    assert sizes("last", 1) == [4, 1, 1] and sizes("last", 0) == [6]
+    assert cls[at["last"]].tolist() == [0] * 6 + [0, 1, 2, 2, 2, 2]
+    assert sizes("ties", 0) == [2, 2, 1, 1] and sizes("ties", 1) == [3, 3]
+    assert sums[at["ties"]].tolist() == [[10, 2, 2, 1], [18, 3, 3, 0]]
+    assert h[at["ties"], 0].tolist() == [10 / 36, 18 / 36, (10 + 2 * (4 + 2 + 2)) / 36, 6 / 10, 26 / 30]
+    assert h[at["ties"], 1].tolist() == [18 / 36, 1.0, 1.0, 9 / 18, 18 / 30]
+    assert sizes("noseg", 0) == [6] and sums[at["noseg"], 1].tolist() == [36, 6, 0, 0]
+    for nm in ("empty", "reversed"):
+        assert not k[at[nm]].any() and not counts[at[nm]].any() and not sums[at[nm]].any()
+        assert (cls[at[nm]] == 255).all() and np.isnan(h[at[nm]]).all()
+    # the long window: samples 0, 2, 4 | 6, 8, 9 stand alone, the others of each population are one class
+    assert named["long"][1] - named["long"][0] > 2048 and len({(r // 8 - named["long"][0] // 8) // 64 % 4 for r in marks.values()}) == 4
+    assert sizes("long", 0) == [3, 1, 1, 1] == sizes("long", 1)
+    assert cls[at["long"]].tolist() == [0, 1, 2, 1, 4, 1] + [0, 1, 2, 3, 1, 1]
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [12, 24, 48, 96])
+def test_hfs_partial_last_word(gpu_lib, n):
+    """Windows that end at n_rows = L = 64 * 5 + 3, no multiple of the rows per 16-byte word; the rows
+    sit in a larger buffer of 0xFF bytes, which would read as segregating rows with every sample set."""
+    import torch
+    L = 64 * 5 + 3
+    rng = np.random.default_rng(n)
+    types = _founder_types(rng, L, n, 4)
+    flags = np.where(rng.random(L) < 0.1, COUNTED | SEG, COUNTED).astype(np.uint8)
+    flags[L - 1] = COUNTED | SEG
+    sizes = [n // 3, n // 3, n - 2 * (n // 3)]
+    masks = _blocks(sizes)
+    ctx, params, rows = _crafted(n, masks, types, flags)
+    big = torch.full((rows.numel() + 4096,), 0xFF, dtype=torch.uint8, device="cuda")
+    big[:rows.numel()] = rows
+    wins = [(3, L), (0, L), (L - 1, L), (L - 9, L), (1, 2)]
+    got = _run_hfs(ctx, big, L, wins)
+    _assert_same(got, ref_hfs(types, flags, masks, sizes, n, wins))
+    assert (got[0][:2] > 1).all()
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_hfs_argument_errors(gpu_lib):
+    import torch
+    from popbam_amd import _lib, workload
+    ctx, params, rows, types, flags = _shape("n12p2")
+    wins = _wins_tensor([(0, 1000)])
+    j = workload.Hfs(ctx, 1)
+    lib, s = ctx.lib, workload.stream_handle()
+    r, w, out = rows.data_ptr(), wins.data_ptr(), C.byref(j.out)
+    assert lib.pbg_hfs_stride(None) == 0 and lib.pbg_hfs_stride(ctx.h) == 6
+    assert lib.pbg_window_hfs(None, r, N_SITES, w, 1, out, s) == _lib.PBG_E_ARG
+    for args in ((None, N_SITES, w, 1, out), (r, N_SITES, None, 1, out), (r, N_SITES, w, 1, None)):
+        assert lib.pbg_window_hfs(ctx.h, *args, s) == _lib.PBG_E_ARG
+        assert lib.pbg_last_error(ctx.h)
+    # pop_n that is not the mask's popcount
+    bad = _params(12, _blocks([6, 6]))
+    bad.pop_n[1] = 5
+    cbad = _lib.Context(bad, 0)
+    assert workload.Hfs(cbad, 1).run(rows, wins, N_SITES) == _lib.PBG_E_ARG
+    assert b"pop_n" in lib.pbg_last_error(cbad.h)
+    cbad.close()
+    # a sample in two populations never reaches the call: pbg_create refuses the context
+    with pytest.raises(_lib.PbgError, match="overlap"):
+        _lib.Context(_params(12, [0b000001111111, 0b111111000000]), 0)
+    # no window: PBG_OK, nothing written
+    none = workload.Hfs(ctx, 0)
+    assert none.run(rows, wins, N_SITES) == _lib.PBG_OK
+    # a window past the rows is never read: an empty window's outputs, reported by pbg_check
+    over = workload.Hfs(ctx, 3)
+    assert over.run(rows, _wins_tensor([(0, N_SITES + 1), (0, 1000), (-1, 10)]), N_SITES) == _lib.PBG_OK
+    assert lib.pbg_check(ctx.h, None) == _lib.PBG_E_RANGE
+    assert j.run(rows, wins, N_SITES) == _lib.PBG_OK
+    ctx.sync_check()
+    for w_ in (0, 2):
+        assert not over.k[w_].any() and not over.counts[w_].any() and not over.sums[w_].any()
+        assert (over.cls[w_] == 255).all() and torch.isnan(over.h[w_]).all()
+    for nm in NAMES:
+        assert getattr(over, nm)[1].cpu().numpy().tobytes() == getattr(j, nm)[0].cpu().numpy().tobytes(), nm
+    assert j.k[0].min() > 0
+
+
+@pytest.mark.gpu
+def test_hfs_interleaves_with_the_other_calls(gpu_lib):
+    """Statistics, joint spectrum, LD decay, D statistics, the haplotype spectrum, the haplotype spectrum
+    again, statistics, with the same pointers on one context and stream: each equals its own stand-alone
+    run on a fresh context byte for byte; two hfs runs give identical bytes; a NULL member of pbg_hfs_out
+    leaves its array untouched and the others correct."""
+    from popbam_amd import _lib, workload
+    n, npops, L = 12, 3, 64 * 1500
+    wins = [(0, L)] + workload.reference_windows(0, L, 10_000) + [(s, s + 40) for s in range(0, 4000, 100)]
+    T = [(0, 1, 2), (0, 2, 1), (1, 2, 0)]
+
+    def fresh():
+        ctx = _lib.Context(workload.default_params(n, npops), 0)
+        syn = workload.SynthPileup(ctx, L, 10, SEED)
+        hp = workload.HotPath(ctx, syn, wins, _lib.PBG_S_ZNS)
+        hp.call()
+        ctx.sync_check()
+        return ctx, hp
+
+    def zns(hp):
+        hp.out.t["ld_val"].fill_(-1.0)
+        hp.out.t["ld_snps"].fill_(-1)
+        hp.window_stats()
+
+    def zns_out(hp):
+        return hp.out.t["ld_snps"].cpu().numpy().copy(), bits(hp.out.t["ld_val"].cpu().numpy()).copy()
+
+    def arrays(x, names):
+        return tuple(getattr(x, k).cpu().numpy().copy() for k in names)
+
+    def same_bytes(got, want, what):
+        for g, w_, nm in zip(got, want, what):
+            assert g.tobytes() == w_.tobytes(), nm
+
+    JN, DN, TN = ("cells", "diffs", "fst"), ("pairs", "r2_sum", "n_var"), ("sums", "d", "fd", "fdm")
+    names_of = {"jsfs": JN, "decay": DN, "dstat": TN, "hfs": NAMES}
+    alone = {}
+    for key, make in (("zns", None), ("jsfs", lambda hp: workload.JointSfs.of(hp)),
+                      ("decay", lambda hp: workload.LdDecay.of(hp, 100, 100)),
+                      ("dstat", lambda hp: workload.DStat.of(hp, T)), ("hfs", lambda hp: workload.Hfs.of(hp))):
+        ctx, hp = fresh()
+        if make is None:
+            zns(hp)
+            ctx.sync_check()
+            alone[key] = zns_out(hp)
+        else:
+            x = make(hp)
+            ctx.sync_check()
+            alone[key] = arrays(x, names_of[key])
+        ctx.close()
+    ak = alone["hfs"][0]
+    assert ak.min() > 0 and (ak == 1).any() and (ak == 4).any()
+
+    ctx, hp = fresh()
+    zns(hp)
+    ctx.sync_check()
+    first = zns_out(hp)
+    zns(hp)   # a cached plan from here on
+    j = workload.JointSfs(ctx, len(wins))
+    j(hp.rows, hp.wins, L)
+    d = workload.LdDecay(ctx, len(wins), 100, 100)
+    d(hp.rows, hp.wins, L)
+    t = workload.DStat(ctx, len(wins), T)
+    t(hp.rows, hp.wins, L)
+    h1 = workload.Hfs(ctx, len(wins))
+    h1(hp.rows, hp.wins, L)
+    h2 = workload.Hfs(ctx, len(wins))
+    h2(hp.rows, hp.wins, L)
+    zns(hp)
+    ctx.sync_check()
+    second = zns_out(hp)
+    for got in (first, second):
+        assert np.array_equal(got[0], alone["zns"][0]) and np.array_equal(got[1], alone["zns"][1])
+    same_bytes(arrays(j, JN), alone["jsfs"], JN)
+    same_bytes(arrays(d, DN), alone["decay"], DN)
+    same_bytes(arrays(t, TN), alone["dstat"], TN)
+    same_bytes(_arrays(h1), alone["hfs"], NAMES)
+    same_bytes(_arrays(h2), _arrays(h1), NAMES)
+    for k, drop in enumerate(NAMES):   # a NULL member: the others as before, the dropped array untouched
+        part = workload.Hfs(ctx, len(wins))
+        getattr(part, drop).fill_(3)
+        setattr(part.out, drop, None)
+        part(hp.rows, hp.wins, L)
+        ctx.sync_check()
+        got = _arrays(part)
+        for m, nm in enumerate(NAMES):
+            if m == k:
+                assert (got[m] == 3).all(), nm
+            else:
+                assert got[m].tobytes() == alone["hfs"][m].tobytes(), (drop, nm)
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,founders", CROSS, ids=[f"n{a}" for a, _ in CROSS])
+def test_hfs_agrees_with_calc_nhaps_on_one_population(gpu_lib, n, founders):
+    """The rows of test_one_population_agrees_with_the_oracles_calc_nhaps on the device: k is nhaps of
+    pbg_window_stats(PBG_S_HAP_K) and 1.0 - (double)Q / (double)(n * n) has the bits of its hap_val."""
+    import torch
+    from popbam_amd import _lib, workload
+    types, flags = _cross_rows(n, founders)
+    ctx = _lib.Context(_one_population(n), 0)
+    rows = torch.from_numpy(harness.rows_from_oracle(types, flags, ctx.row_bytes).copy()).cuda()
+    wt = _wins_tensor(CROSS_WINS)
+    out = workload.WindowOutputs(len(CROSS_WINS), n, 1)
+    so = _lib.PbgStatOpts(_lib.PBG_S_HAP_K, 1, 0, 0)
+    ost = out.struct(("num_sites", "segsites", "nhaps", "hap_val"))
+    ctx.check(ctx.lib.pbg_window_stats(ctx.h, rows.data_ptr(), CROSS_L, wt.data_ptr(), len(CROSS_WINS), C.byref(so),
+                                       C.byref(ost), workload.stream_handle()), "pbg_window_stats")
+    j = workload.Hfs(ctx, len(CROSS_WINS))
+    j(rows, wt, CROSS_L)
+    ctx.sync_check()
+    k, counts, cls, sums, h = _arrays(j)
+    _assert_same((k, counts, cls, sums, h), ref_hfs(types, flags, [(1 << n) - 1], [n], n, CROSS_WINS))
+    nhaps = out.t["nhaps"].cpu().numpy().reshape(-1)
+    hap_val = out.t["hap_val"].cpu().numpy().reshape(-1)
+    assert nhaps.tolist() == k[:, 0].tolist()
+    want = np.array([1.0 - float(q) / float(n * n) for q in sums[:, 0, 0].tolist()], np.float64)
+    assert bits(hap_val).tolist() == bits(want).tolist()
+    ctx.close()
+
+
+BOUNDS_SNIPPET = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, {repo!r}); sys.path.insert(0, {repo!r} + "/tests")
+from popbam_amd import _lib, workload
+assert _lib.load().pbg_build_info() == b"bounds"
+params = workload.default_params({n}, {npops})
+for i, m in enumerate({masks!r}):
+    params.set_pop_mask(i, m)
+    params.pop_n[i] = bin(m).count("1")
+ctx = _lib.Context(params, 0)
+syn = workload.SynthPileup(ctx, {n_sites}, 10, {seed})
+hp = workload.HotPath(ctx, syn, {wins!r}, _lib.PBG_S_SFS)
+hp.call()
+ctx.sync_check()
+j = workload.Hfs.of(hp)
+ctx.sync_check()
+np.savez({out!r}, rows=hp.rows.cpu().numpy(), **{{k: getattr(j, k).cpu().numpy() for k in workload.Hfs.NAMES}})
+ctx.close()
+print("ok")
+"""
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["n12p2", "n40p2i", "n126p3"])
+def test_hfs_under_the_bounds_build(gpu_lib, tmp_path, name):
+    """Called rows through the PBG_BOUNDS build (a fresh process): the same rows and the checker's numbers."""
+    if not os.path.exists(BOUNDS_LIB):
+        pytest.skip("the bounds build is not there (make bounds)")
+    ctx, params, rows, types, flags = _shape(name)
+    n, masks = SHAPES[name]
+    out = str(tmp_path / "bounds.npz")
+    env = dict(os.environ, POPBAM_GPU_LIB=BOUNDS_LIB)
+    wins = _windows(N_SITES)
+    r = subprocess.run([sys.executable, "-c", BOUNDS_SNIPPET.format(repo=REPO, n=n, npops=len(masks), masks=masks,
+                                                                   n_sites=N_SITES, seed=SEED + n, out=out, wins=wins)],
+                       env=env, capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
+    z = np.load(out)
+    assert np.array_equal(z["rows"], rows.cpu().numpy())
+    pop_n = [bin(m).count("1") for m in masks]
+    _assert_same(tuple(z[k] for k in NAMES), ref_hfs(types, flags, masks, pop_n, n, wins), "bounds")
+
+
+# ---- command lines -----------------------------------------------------------------------
+def _native(argv, timeout=120):
+    e = dict(os.environ)
+    e.pop("WORLD_SIZE", None)
+    r = subprocess.run([BIN, *argv], capture_output=True, timeout=timeout, env=e)
+    return r.returncode, r.stdout.decode(), r.stderr.decode()
+
+
+def _haplo_case(name, output):
+    args = ["haplo", "-w", "1"] + (["-o", str(output)] if output else [])
+    cases = fixtures.load_case(name)["meta"]["cases"]
+    return next(cs for cs in cases if cs["args"] == args)
+
+
+def _argv(name, cs):
+    d = fixtures.load_case(name)["dir"]
+    a = cs["args"]
+    return [a[0], "-f", os.path.join(d, "ref.fa")] + list(a[1:]) + [os.path.join(d, "in.bam"), cs["region"]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("output", [0, 1, 2])
+@pytest.mark.parametrize("name", ["g01_base", "g02_interleaved"])
+def test_hfs_command_line(gpu_lib, name, output):
+    """`popbam haplo -w 1 [-o N]` through cli.run and the native binary: without --hfs the golden text;
+    with it the same text from both, every line the golden line plus, per population, H1, H12, H123,
+    H2H1, Hd and the class sizes, which are the checker's on the oracle's rows for the command."""
+    from popbam_amd import workload
+    cs = _haplo_case(name, output)
+    argv = _argv(name, cs)
+    gold_text = fixtures.golden_text(name, cs["stdout"])
+    gold = gold_text.splitlines()
+    st = harness.Setup(name, cs["args"] + ["--hfs"], cs["region"])
+    assert (st.opts.hfs, st.opts.output) == (1, output)
+    _, types, _, flags = harness.oracle_call(st.orc_params(), st.batch)
+    wins = workload.reference_windows(st.beg, st.end, st.opts.win_size)
+    pops, npop = st.sm.pops, len(st.sm.pops)
+    k, counts, cls, sums, h = ref_hfs(types, flags, st.masks, st.pop_n, st.sm.n, wins)
+    plain = cli.run(argv[0], argv[1:])
+    rc, nat_plain, err = _native(argv)
+    assert rc == 0, err
+    assert plain == gold_text == nat_plain
+    ours = cli.run(argv[0], argv[1:] + ["--hfs"])
+    rc, nat, err = _native(argv[:1] + ["--hfs"] + argv[1:])   # the token in front here, at the end there
+    assert rc == 0, err
+    assert nat == ours
+    lines = ours.splitlines()
+    assert len(lines) == len(gold) == len(wins) > 0
+    for w, (gl, ln) in enumerate(zip(gold, lines)):
+        assert ln.startswith(gl + "\tH1["), (gl, ln)
+        ext = ln[len(gl):].split("\t")[1:]
+        assert len(ext) == 12 * npop
+        for i, p in enumerate(pops):
+            f = ext[12 * i:12 * i + 12]
+            assert f[0:10:2] == [f"{nm}[{p}]:" for nm in HNAMES] and f[10] == f"hfs[{p}]:", f
+            for txt, v in zip(f[1:10:2], h[w, i].tolist()):
+                assert (txt.strip() == "NA") if np.isnan(v) else (txt == "%.5f" % v), (w, p, txt, v)
+            assert [int(x) for x in f[11].split(",")] == counts[w, i, :k[w, i]].tolist(), (w, p)
+    assert k.max() > 1 and (name != "g01_base" or (counts[:, :, 0] > 1).any())   # g01 has classes of several samples
