@@ -83,6 +83,23 @@ std::vector<int32_t> jsfs_offsets(const pbg::DevParams &dp) {
     off.push_back(at);
     return off;
 }
+
+// argument checks shared by the side tables' calls; `what` is the call's prefix in the message
+// ("jsfs", "dstat", "hfs").  The kernels count within pop_mask and subtract from or divide by pop_n.
+int check_pop_sizes(pbg_ctx *c, const char *what) {
+    for (int i = 0; i < c->dp.npops; ++i)
+        if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
+            return fail(c, PBG_E_ARG, std::string(what) + ": pop_n must be the number of samples in pop_mask");
+    return PBG_OK;
+}
+// the outgroup's sample index to hand the kernel (-1: the context does not flip)
+int check_outidx(pbg_ctx *c, const char *what, int32_t outidx, int32_t *flip_idx) {
+    *flip_idx = -1;
+    if (!(c->dp.flag & PBG_F_OUTGROUP)) return PBG_OK;
+    if (outidx < 0 || outidx >= c->dp.n) return fail(c, PBG_E_ARG, std::string(what) + ": outidx must be a sample index");
+    *flip_idx = outidx;
+    return PBG_OK;
+}
 }  // namespace
 
 namespace pbg {
@@ -727,8 +744,8 @@ int pbg_jsfs_pair_offset(const pbg_ctx *c, int i, int j) {
 int pbg_window_jsfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
                     const pbg_jsfs_opts *o, const pbg_jsfs_out *out, void *stream) {
     if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
-    const bool flip = (c->dp.flag & PBG_F_OUTGROUP) != 0;
-    if (flip && (o->outidx < 0 || o->outidx >= c->dp.n)) return fail(c, PBG_E_ARG, "jsfs: outidx must be a sample index");
+    int32_t flip_idx;
+    if (int rc = check_outidx(c, "jsfs", o->outidx, &flip_idx)) return rc;
     const int np = c->dp.npops;
     if (np < 2 || n_win == 0) return PBG_OK;
     if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
@@ -736,9 +753,7 @@ int pbg_window_jsfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_win
     HIPCHK(c, hipSetDevice(c->device));
     if (!pl.built) {
         // the counts are popcounts within the masks, so the cell layout (from pop_n) needs them equal
-        for (int i = 0; i < np; ++i)
-            if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
-                return fail(c, PBG_E_ARG, "jsfs: pop_n must be the number of samples in pop_mask");
+        if (int rc = check_pop_sizes(c, "jsfs")) return rc;
         const std::vector<int32_t> off = jsfs_offsets(c->dp);
         std::vector<uint32_t> pairs;
         for (int i = 0; i < np; ++i)
@@ -774,7 +789,7 @@ int pbg_window_jsfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_win
     A.n_groups = pl.n_groups;
     A.n_cells = pl.n_cells;
     A.lds_cells = pl.lds_cells;
-    A.outidx = flip ? o->outidx : -1;
+    A.outidx = flip_idx;
     A.err = c->d_err;
     A.cells = out->cells;
     A.diffs = out->diffs;
@@ -789,8 +804,8 @@ int pbg_window_dstat(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
     if (o->n_triples < 0 || o->n_triples > PBG_DSTAT_MAX_TRIPLES)
         return fail(c, PBG_E_ARG, "dstat: n_triples must be in [0, " + std::to_string(PBG_DSTAT_MAX_TRIPLES) + "]");
     if (o->n_triples > 0 && !o->triples) return fail(c, PBG_E_ARG, "dstat: null triple list");
-    const bool flip = (c->dp.flag & PBG_F_OUTGROUP) != 0;
-    if (flip && (o->outidx < 0 || o->outidx >= c->dp.n)) return fail(c, PBG_E_ARG, "dstat: outidx must be a sample index");
+    int32_t flip_idx;
+    if (int rc = check_outidx(c, "dstat", o->outidx, &flip_idx)) return rc;
     const int np = c->dp.npops;
     std::vector<uint32_t> words((size_t)o->n_triples);
     for (int t = 0; t < o->n_triples; ++t) {
@@ -804,9 +819,7 @@ int pbg_window_dstat(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
     if (o->n_triples == 0 || n_win == 0) return PBG_OK;
     if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
     // the counts are popcounts within the masks and are parked as bytes: n - count needs pop_n to be them
-    for (int i = 0; i < np; ++i)
-        if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
-            return fail(c, PBG_E_ARG, "dstat: pop_n must be the number of samples in pop_mask");
+    if (int rc = check_pop_sizes(c, "dstat")) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // the list's device copy, by content (pbg_ctx.h): written once, never overwritten
     const uint32_t *d_words = nullptr;
@@ -834,7 +847,7 @@ int pbg_window_dstat(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
     A.wins = wins;
     A.triples = d_words;
     A.n_triples = o->n_triples;
-    A.outidx = flip ? o->outidx : -1;
+    A.outidx = flip_idx;
     A.err = c->d_err;
     A.sums = out->sums;
     A.d = out->d;
@@ -849,9 +862,7 @@ int pbg_window_hfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wind
     if (!c || !rows || !wins || !out) return fail(c, PBG_E_ARG, "null argument");
     // a class label is a rank inside pop_mask and the doubles divide by pop_n: they must agree.  (A sample
     // in two populations cannot get here: pbg_create refuses overlapping masks.)
-    for (int i = 0; i < c->dp.npops; ++i)
-        if (__builtin_popcountll(c->dp.pop_mask[i]) + __builtin_popcountll(c->dp.pop_mask_hi[i]) != c->dp.pop_n[i])
-            return fail(c, PBG_E_ARG, "hfs: pop_n must be the number of samples in pop_mask");
+    if (int rc = check_pop_sizes(c, "hfs")) return rc;
     if (n_win == 0) return PBG_OK;
     if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
     HIPCHK(c, hipSetDevice(c->device));

@@ -7,10 +7,10 @@
 // denominators of f_d and f_dM -- and three doubles formed from them (include/popbam_gpu.h has the
 // definition).
 //
-// One workgroup per window.  The rows are streamed as in jsfs_kernel.hip: every wave takes 16-byte
-// row words, the next ones loaded ahead, packs the segregating rows it finds into a queue of its own
-// (wave prefix sum) and parks every queued row's per-population counts as bytes, flip included.  The
-// triple work reads three bytes per (row, triple); its lane mapping follows the list's length:
+// One workgroup per window.  The window's segregating rows come through the row stream and every
+// queued row's per-population counts, flip included, through the count batches (both in
+// pbg_rows.h).  The triple work reads three bytes per (row, triple) of a batch; its lane mapping
+// follows the list's length:
 //   up to kDstatLaneTriples triples: with G the power of two >= n_triples, lane l owns triple
 //     l & (G - 1) for the whole window and takes rows l / G, l / G + 64 / G, ... of every batch; its
 //     six sums stay in registers, and after the last row a butterfly over the lanes of one triple and
@@ -32,33 +32,6 @@ namespace pbg {
 
 namespace {
 
-// a queued row: the sample bits in the narrowest word that holds them
-template <int RB>
-struct DstatQ {
-    using T = uint32_t;
-    __device__ __forceinline__ static T put(uint64_t t) { return (uint32_t)t; }
-    __device__ __forceinline__ static uint64_t get(T q) { return q; }
-};
-template <>
-struct DstatQ<8> {
-    using T = uint64_t;
-    __device__ __forceinline__ static T put(uint64_t t) { return t; }
-    __device__ __forceinline__ static uint64_t get(T q) { return q; }
-};
-template <>
-struct DstatQ<16> {
-    using T = M2;
-    __device__ __forceinline__ static T put(M2 t) { return t; }
-    __device__ __forceinline__ static M2 get(T q) { return q; }
-};
-
-// LDS written by some lanes of a wave, read by others of the same wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // the six sums of one triple (named members: they stay in registers)
 struct Sums6 {
     long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
@@ -79,8 +52,6 @@ __device__ __forceinline__ void dstat_terms(int a, int b, int c, int n1, int n2,
     s.s5 += d1 ? 0 : c * (c * n2 - b * n3);
 }
 
-__device__ __forceinline__ double dstat_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
-
 // the unit is built with -ffp-contract=off: every conversion, division and sum is its own IEEE operation
 __device__ __forceinline__ void dstat_ratios(const Sums6 &s, int n1, int n2, int n3, double &d, double &fd, double &fdm) {
     const long long l1 = n1, l2 = n2, l3 = n3;
@@ -88,10 +59,10 @@ __device__ __forceinline__ void dstat_ratios(const Sums6 &s, int n1, int n2, int
     const double num = diff / (double)(l1 * l2 * l3);
     const double den = (double)s.s2 / (double)(l1 * l2 * l2) + (double)s.s3 / (double)(l1 * l3 * l3);
     const double den2 = (double)s.s4 / (double)(l2 * l1 * l1) + (double)s.s5 / (double)(l2 * l3 * l3);
-    d = s.s0 + s.s1 == 0 ? dstat_nan() : diff / (double)(s.s0 + s.s1);
-    fd = den == 0.0 ? dstat_nan() : num / den;
+    d = s.s0 + s.s1 == 0 ? quiet_nan() : diff / (double)(s.s0 + s.s1);
+    fd = den == 0.0 ? quiet_nan() : num / den;
     const double dm = s.s0 >= s.s1 ? den : den2;
-    fdm = dm == 0.0 ? dstat_nan() : num / dm;
+    fdm = dm == 0.0 ? quiet_nan() : num / dm;
 }
 
 }  // namespace
@@ -99,40 +70,19 @@ __device__ __forceinline__ void dstat_ratios(const Sums6 &s, int n1, int n2, int
 template <int RB>
 __global__ __launch_bounds__(256) void window_dstat_kernel(DevParams P, const void *__restrict__ rows, uint32_t n_rows,
                                                            uint32_t n_win, DstatArgs A) {
-    using M = typename RowMask<RB>::T;
-    using Q = DstatQ<RB>;
-    constexpr int R = 16 / RB;
-    constexpr int QCAP = 64 * R;   // the rows one wave decodes per iteration
+    using Q = QueuedRow<RB>;
     extern __shared__ __align__(16) unsigned char sm[];
     unsigned long long *s_acc = reinterpret_cast<unsigned long long *>(sm);   // [6][ntg] of the group
-    __shared__ typename Q::T s_q[4][QCAP];
-    __shared__ uint8_t s_cnt[4][kDstatCntBytes];
-    __shared__ uint64_t s_pm[PBG_MAX_POPS], s_pmh[PBG_MAX_POPS];
-    __shared__ int32_t s_pn[PBG_MAX_POPS];
+    __shared__ typename Q::T s_q[4][64 * (16 / RB)];
+    __shared__ uint8_t s_cnt[4][kCntBytes];
+    __shared__ PopLds s_pop;
     __shared__ uint32_t s_tw[kDstatLdsTriples];   // the group's triple words
     const int np = P.npops, tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint32_t w = blockIdx.x;
     if (w >= n_win) return;
-    if (tid < np) {
-        s_pm[tid] = P.pop_mask[tid];
-        s_pmh[tid] = P.pop_mask_hi[tid];
-        s_pn[tid] = P.pop_n[tid];
-    }
-    auto pmask = [&](int i) -> M {
-        if constexpr (RB == 16) return M2{s_pm[i], s_pmh[i]};
-        else return s_pm[i];
-    };
-    int64_t wb = A.wins[w].beg, we = A.wins[w].end;
-    if (we <= wb) {
-        wb = we = 0;   // an empty window, whatever its coordinates
-    } else if (wb < 0 || we > (int64_t)n_rows) {
-        // a window outside the rows is reported (pbg_check -> PBG_E_RANGE) and never read
-        if (tid == 0) atomicOr(A.err, 4);
-        wb = we = 0;
-    }
-    const int64_t c0 = wb / R, c1 = (we + R - 1) / R;
-    const int batch = kDstatCntBytes / np;   // rows whose counts are staged together (>= 16)
-    const int outidx = A.outidx;
+    s_pop.stage(P, tid);
+    const int32_t *s_pn = s_pop.pn;
+    const WindowRows win = clamp_window(A.wins[w], n_rows, A.err, tid);
     const int nt = A.n_triples;
     // short lists: lane -> (triple my, first row slot) for the whole window
     const bool by_lane = nt <= kDstatLaneTriples;   // kernel-uniform
@@ -155,42 +105,9 @@ __global__ __launch_bounds__(256) void window_dstat_kernel(DevParams P, const vo
         }
         Sums6 acc;
 
-        // ---- the window's rows: every wave takes 64 words at a time, the next ones loaded ahead
-        uint4 nxt = make_uint4(0, 0, 0, 0);
-        if (c0 + wave * 64 + lane < c1) nxt = load_row_word<RB>(rows, n_rows, c0 + wave * 64 + lane);
-        for (int64_t cb = c0 + wave * 64; cb < c1; cb += 256) {   // wave-uniform
-            const int64_t c = cb + lane;
-            const uint4 q = nxt;
-            nxt = c + 256 < c1 ? load_row_word<RB>(rows, n_rows, c + 256) : make_uint4(0, 0, 0, 0);
-            M t[R];
-            uint32_t vm = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int64_t ri = c * R + r;
-                bool cnt, sg;
-                row_in_word<RB>(q, r, t[r], cnt, sg);
-                vm |= (c < c1 && ri >= wb && ri < we && sg) ? (1u << r) : 0u;
-            }
-            const uint32_t ls = (uint32_t)__popc(vm);
-            const uint32_t incl = wave_incl_scan_s(ls);
-            uint32_t j = incl - ls;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if ((vm >> r) & 1u) s_q[wave][j++] = Q::put(t[r]);
-            const int nq = __builtin_amdgcn_readlane((int)incl, 63);
-            if (nq == 0) continue;
-            wave_sync();
-            for (int b0 = 0; b0 < nq; b0 += batch) {
-                const int nb = nq - b0 < batch ? nq - b0 : batch;
-                // (row, population): each count once, flipped when the outgroup is derived
-                for (int k = lane; k < nb * np; k += 64) {
-                    const int row = k / np, i = k - row * np;
-                    const M tt = Q::get(s_q[wave][b0 + row]);
-                    int f = (int)pc(tt & pmask(i));
-                    if (outidx >= 0 && bit(tt, outidx)) f = s_pn[i] - f;
-                    s_cnt[wave][k] = (uint8_t)f;
-                }
-                wave_sync();
+        // ---- the window's rows (pbg_rows.h): one word loaded ahead
+        stream_window_rows<RB, 1>(rows, n_rows, win, wave, lane, s_q[wave], [&](int nq) {
+            count_batches<RB>(s_q[wave], nq, s_pop, np, A.outidx, lane, s_cnt[wave], [&](int nb) {
                 if (by_lane) {
                     if (have)
                         for (int row = slot; row < nb; row += step) {
@@ -210,9 +127,8 @@ __global__ __launch_bounds__(256) void window_dstat_kernel(DevParams P, const vo
                         v.each([&](int x, long long sx) { atomicAdd(&s_acc[x * ntg + tr], (unsigned long long)sx); });
                     }
                 }
-                wave_sync();   // the next batch's counts, the next iteration's queue
-            }
-        }
+            });
+        });
         if (by_lane) {
             // the lanes of one triple are G apart: an integer butterfly, then one add per wave
             acc.each([&](int x, long long v) {
@@ -242,22 +158,14 @@ __global__ __launch_bounds__(256) void window_dstat_kernel(DevParams P, const vo
     }
 }
 
-template __global__ void window_dstat_kernel<2>(DevParams, const void *, uint32_t, uint32_t, DstatArgs);
-template __global__ void window_dstat_kernel<4>(DevParams, const void *, uint32_t, uint32_t, DstatArgs);
-template __global__ void window_dstat_kernel<8>(DevParams, const void *, uint32_t, uint32_t, DstatArgs);
-template __global__ void window_dstat_kernel<16>(DevParams, const void *, uint32_t, uint32_t, DstatArgs);
-
 hipError_t launch_window_dstat(int rb, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                                const DstatArgs &A, hipStream_t stream) {
     if (n_win == 0 || A.n_triples <= 0) return hipSuccess;
     const dim3 g(n_win), b(256);
     const size_t lds = (size_t)(A.n_triples < kDstatLdsTriples ? A.n_triples : kDstatLdsTriples) * 48;
-    switch (rb) {
-        case 2: hipLaunchKernelGGL(window_dstat_kernel<2>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-        case 4: hipLaunchKernelGGL(window_dstat_kernel<4>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-        case 8: hipLaunchKernelGGL(window_dstat_kernel<8>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-        default: hipLaunchKernelGGL(window_dstat_kernel<16>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-    }
+    dispatch_rb(rb, [&](auto RB) {
+        hipLaunchKernelGGL(window_dstat_kernel<decltype(RB)::value>, g, b, lds, stream, P, rows, n_rows, n_win, A);
+    });
     return hipGetLastError();
 }
 

@@ -7,10 +7,9 @@
 // whose bit u says that s and u differ somewhere.  The lowest set bit of ~D_s inside the population's
 // mask is the class's lowest member (equality is an equivalence), its rank inside the mask the label.
 //
-// One workgroup per window.  The rows are streamed as in dstat_kernel.hip: every wave takes 16-byte
-// row words, the next two loaded ahead, and packs the segregating rows it finds into a queue of its
-// own (wave prefix sum).  With G the power of two >= n_samples (at most 64), lane l owns sample
-// l & (G - 1) for the whole window -- above 64 samples also sample l + 64 -- and takes queued rows
+// One workgroup per window.  The window's segregating rows come through the row stream
+// (pbg_rows.h), a wave's queue at a time.  With G the power of two >= n_samples (at most 64), lane l
+// owns sample l & (G - 1) for the whole window -- above 64 samples also sample l + 64 -- and takes queued rows
 // l / G, l / G + 64 / G, ...; its masks stay in registers.  After the last row an OR butterfly over
 // the lanes of one sample and one integer LDS OR per sample and wave merge them.  Then the workgroup
 // labels the samples, counts the class sizes in an LDS histogram, sorts each population's sizes by
@@ -27,11 +26,10 @@ namespace pbg {
 
 namespace {
 
-// a queued row and a difference mask: the narrowest word that holds the sample bits
+// a difference mask has the type of a queued row (QueuedRow, pbg_rows.h)
 template <int RB>
-struct HfsQ {
-    using T = uint32_t;
-    __device__ __forceinline__ static T put(uint64_t t) { return (uint32_t)t; }
+struct HfsQ : QueuedRow<RB> {
+    using T = typename QueuedRow<RB>::T;
     __device__ __forceinline__ static T zero() { return 0u; }
     // D |= (bit s of t ? ~t : t)
     __device__ __forceinline__ static void differ(T &d, T t, int s) { d |= t ^ (0u - ((t >> s) & 1u)); }
@@ -40,9 +38,7 @@ struct HfsQ {
     __device__ __forceinline__ static uint64_t hi(T) { return 0; }
 };
 template <>
-struct HfsQ<8> {
-    using T = uint64_t;
-    __device__ __forceinline__ static T put(uint64_t t) { return t; }
+struct HfsQ<8> : QueuedRow<8> {
     __device__ __forceinline__ static T zero() { return 0ull; }
     __device__ __forceinline__ static void differ(T &d, T t, int s) { d |= t ^ (0ull - ((t >> s) & 1ull)); }
     __device__ __forceinline__ static void merge(T &d, int dd) { d |= (uint64_t)__shfl_xor((unsigned long long)d, dd, 64); }
@@ -50,9 +46,7 @@ struct HfsQ<8> {
     __device__ __forceinline__ static uint64_t hi(T) { return 0; }
 };
 template <>
-struct HfsQ<16> {
-    using T = M2;
-    __device__ __forceinline__ static T put(M2 t) { return t; }
+struct HfsQ<16> : QueuedRow<16> {
     __device__ __forceinline__ static T zero() { return M2{0ull, 0ull}; }
     __device__ __forceinline__ static void differ(T &d, T t, int s) {
         const uint64_t m = 0ull - (uint64_t)bit(t, s);
@@ -67,41 +61,24 @@ struct HfsQ<16> {
     __device__ __forceinline__ static uint64_t hi(T d) { return d.hi; }
 };
 
-// LDS written by some lanes of a wave, read by others of the same wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double hfs_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
-
 }  // namespace
 
 template <int RB>
 __global__ __launch_bounds__(256) void window_hfs_kernel(DevParams P, const void *__restrict__ rows, uint32_t n_rows,
                                                          uint32_t n_win, HfsArgs A) {
-    using M = typename RowMask<RB>::T;
     using Q = HfsQ<RB>;
     using D = typename Q::T;
-    constexpr int R = 16 / RB;
-    constexpr int QCAP = 64 * R;   // the rows one wave decodes per iteration
-    __shared__ D s_q[4][QCAP];
+    __shared__ D s_q[4][64 * (16 / RB)];
     __shared__ unsigned long long s_dlo[kHfsSlots], s_dhi[kHfsSlots];   // the samples' difference masks
     __shared__ int32_t s_hist[kHfsSlots], s_sorted[kHfsSlots];          // class sizes, by population (pop_start)
-    __shared__ uint64_t s_pm[PBG_MAX_POPS], s_pmh[PBG_MAX_POPS];
-    __shared__ int32_t s_pn[PBG_MAX_POPS];
+    __shared__ PopLds s_pop;
     __shared__ int16_t s_pst[PBG_MAX_POPS + 1];
     __shared__ int8_t s_spop[kHfsSlots];    // population of a sample
     __shared__ int8_t s_slpop[kHfsSlots];   // population of a histogram slot
     const int n = P.n, np = P.npops, tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint32_t w = blockIdx.x;
     if (w >= n_win) return;
-    if (tid < np) {
-        s_pm[tid] = P.pop_mask[tid];
-        s_pmh[tid] = P.pop_mask_hi[tid];
-        s_pn[tid] = P.pop_n[tid];
-    }
+    s_pop.stage(P, tid);
     if (tid <= np) s_pst[tid] = P.pop_start[tid];
     if (tid < kHfsSlots) {
         s_dlo[tid] = 0;
@@ -110,18 +87,8 @@ __global__ __launch_bounds__(256) void window_hfs_kernel(DevParams P, const void
         s_spop[tid] = tid < n ? P.sample_pop[tid] : (int8_t)-1;
         s_slpop[tid] = tid < P.pop_start[np] ? P.sample_pop[P.pop_member[tid]] : (int8_t)-1;
     }
-    int64_t wb = A.wins[w].beg, we = A.wins[w].end;
-    bool empty = false;
-    if (we <= wb) {
-        wb = we = 0;   // an empty window, whatever its coordinates
-        empty = true;
-    } else if (wb < 0 || we > (int64_t)n_rows) {
-        // a window outside the rows is reported (pbg_check -> PBG_E_RANGE) and never read
-        if (tid == 0) atomicOr(A.err, 4);
-        wb = we = 0;
-        empty = true;
-    }
-    const int64_t c0 = wb / R, c1 = (we + R - 1) / R;
+    const WindowRows win = clamp_window(A.wins[w], n_rows, A.err, tid);
+    const bool empty = win.empty;
     // lane -> (sample sa, and sb = sa + 64 above 64 samples; first row slot) for the whole window
     int G = 1;
     while (G < n && G < 64) G <<= 1;
@@ -129,41 +96,15 @@ __global__ __launch_bounds__(256) void window_hfs_kernel(DevParams P, const void
     D da = Q::zero(), db = Q::zero();
     __syncthreads();   // the zeroed masks
 
-    // ---- the window's rows: every wave takes 64 words at a time, the next two loaded ahead (a window
-    // is one workgroup, so a launch of few, long windows has little else in flight to hide the latency)
-    uint4 nxt = make_uint4(0, 0, 0, 0), nxt2 = nxt;
-    if (c0 + wave * 64 + lane < c1) nxt = load_row_word<RB>(rows, n_rows, c0 + wave * 64 + lane);
-    if (c0 + wave * 64 + lane + 256 < c1) nxt2 = load_row_word<RB>(rows, n_rows, c0 + wave * 64 + lane + 256);
-    for (int64_t cb = c0 + wave * 64; cb < c1; cb += 256) {   // wave-uniform
-        const int64_t c = cb + lane;
-        const uint4 q = nxt;
-        nxt = nxt2;
-        nxt2 = c + 512 < c1 ? load_row_word<RB>(rows, n_rows, c + 512) : make_uint4(0, 0, 0, 0);
-        M t[R];
-        uint32_t vm = 0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int64_t ri = c * R + r;
-            bool cnt, sg;
-            row_in_word<RB>(q, r, t[r], cnt, sg);
-            vm |= (c < c1 && ri >= wb && ri < we && sg) ? (1u << r) : 0u;
-        }
-        const uint32_t ls = (uint32_t)__popc(vm);
-        const uint32_t incl = wave_incl_scan_s(ls);
-        uint32_t j = incl - ls;   // j + ls <= incl of lane 63 <= 64 * R = QCAP
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            if ((vm >> r) & 1u) s_q[wave][j++] = Q::put(t[r]);
-        const int nq = __builtin_amdgcn_readlane((int)incl, 63);
-        if (nq == 0) continue;
-        wave_sync();
+    // ---- the window's rows (pbg_rows.h): two words loaded ahead (a window is one workgroup, so a
+    // launch of few, long windows has little else in flight to hide the latency)
+    stream_window_rows<RB, 2>(rows, n_rows, win, wave, lane, s_q[wave], [&](int nq) {
         for (int row = slot; row < nq; row += step) {
             const D tt = s_q[wave][row];
             Q::differ(da, tt, sa);
             if constexpr (RB == 16) Q::differ(db, tt, sb & 127);   // counts only when sb < n
         }
-        wave_sync();   // the next iteration's queue
-    }
+    });
     // the lanes of one sample are G apart: an OR butterfly, then one LDS OR per sample and wave
     for (int dd = 32; dd >= G; dd >>= 1) {
         Q::merge(da, dd);
@@ -187,13 +128,13 @@ __global__ __launch_bounds__(256) void window_hfs_kernel(DevParams P, const void
         int label = 255;
         if (i >= 0 && !empty) {
             // bit tid of the candidates is always set (a sample equals itself), so a lower word decides first
-            const uint64_t lo = ~s_dlo[tid] & s_pm[i], hi = ~s_dhi[tid] & s_pmh[i];
+            const uint64_t lo = ~s_dlo[tid] & s_pop.pm[i], hi = ~s_dhi[tid] & s_pop.pmh[i];
             if (lo) {
                 const int f = __builtin_ctzll(lo);
-                label = (int)pc(s_pm[i] & ((1ull << f) - 1ull));
+                label = (int)pc(s_pop.pm[i] & ((1ull << f) - 1ull));
             } else {
                 const int f = __builtin_ctzll(hi | (1ull << 63));
-                label = (int)(pc(s_pm[i]) + pc(s_pmh[i] & ((1ull << f) - 1ull)));
+                label = (int)(pc(s_pop.pm[i]) + pc(s_pop.pmh[i] & ((1ull << f) - 1ull)));
             }
             atomicAdd(&s_hist[s_pst[i] + label], 1);   // label < the population's members
         }
@@ -244,8 +185,8 @@ __global__ __launch_bounds__(256) void window_hfs_kernel(DevParams P, const void
         }
         if (A.h) {
             // the unit is built with -ffp-contract=off: every conversion and division is its own IEEE operation
-            const long long ni = s_pn[i], n2 = ni * ni;
-            double h1 = hfs_nan(), h12 = h1, h123 = h1, h2h1 = h1, hd = h1;
+            const long long ni = s_pop.pn[i], n2 = ni * ni;
+            double h1 = quiet_nan(), h12 = h1, h123 = h1, h2h1 = h1, hd = h1;
             if (!empty) {
                 h1 = (double)qq / (double)n2;
                 h12 = (double)(qq + 2 * x1 * x2) / (double)n2;
@@ -262,21 +203,13 @@ __global__ __launch_bounds__(256) void window_hfs_kernel(DevParams P, const void
     }
 }
 
-template __global__ void window_hfs_kernel<2>(DevParams, const void *, uint32_t, uint32_t, HfsArgs);
-template __global__ void window_hfs_kernel<4>(DevParams, const void *, uint32_t, uint32_t, HfsArgs);
-template __global__ void window_hfs_kernel<8>(DevParams, const void *, uint32_t, uint32_t, HfsArgs);
-template __global__ void window_hfs_kernel<16>(DevParams, const void *, uint32_t, uint32_t, HfsArgs);
-
 hipError_t launch_window_hfs(int rb, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                              const HfsArgs &A, hipStream_t stream) {
     if (n_win == 0) return hipSuccess;
     const dim3 g(n_win), b(256);
-    switch (rb) {
-        case 2: hipLaunchKernelGGL(window_hfs_kernel<2>, g, b, 0, stream, P, rows, n_rows, n_win, A); break;
-        case 4: hipLaunchKernelGGL(window_hfs_kernel<4>, g, b, 0, stream, P, rows, n_rows, n_win, A); break;
-        case 8: hipLaunchKernelGGL(window_hfs_kernel<8>, g, b, 0, stream, P, rows, n_rows, n_win, A); break;
-        default: hipLaunchKernelGGL(window_hfs_kernel<16>, g, b, 0, stream, P, rows, n_rows, n_win, A); break;
-    }
+    dispatch_rb(rb, [&](auto RB) {
+        hipLaunchKernelGGL(window_hfs_kernel<decltype(RB)::value>, g, b, 0, stream, P, rows, n_rows, n_win, A);
+    });
     return hipGetLastError();
 }
 

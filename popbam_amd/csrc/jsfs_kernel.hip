@@ -9,13 +9,11 @@
 //
 // One workgroup per window, the histogram in LDS.  The pairs are taken in groups of consecutive
 // pairs whose cells fit kJsfsLdsCells (the host plans them; most contexts have one group); per group
-// every wave streams 16-byte row words of the window, packs the segregating rows it finds into a
-// queue of its own (wave prefix sum), then works through flat item lists so that no lane idles
-// behind another lane's row: (row, population) items form each count once and park it as a byte,
-// (row, pair) items read two bytes and bump one cell with an integer LDS atomic.  The counts are
-// staged for kJsfsCntBytes / n_pops rows at a time.  Integer atomics are order-free: two runs give
-// the same bytes.  No list of sites outlives an iteration, so there is no capacity and no workspace.
-// After a group's rows: the cells are copied out, the three sums are int64 sums of cell * weight (a
+// the window's segregating rows come through the row stream and every queued row's per-population
+// counts through the count batches (both in pbg_rows.h).  The work is flat item lists, so that no
+// lane idles behind another lane's row: after the (row, population) items of a batch, (row, pair)
+// items read two bytes and bump one cell with an integer LDS atomic.  Integer atomics are
+// order-free: two runs give the same bytes.  After a group's rows: the cells are copied out, the three sums are int64 sums of cell * weight (a
 // lane per pair of up to 64 cells, a wave per larger pair with an integer butterfly) and one lane
 // per pair forms Fst.
 #include "pbg_common.h"
@@ -29,33 +27,6 @@ namespace pbg {
 
 namespace {
 
-// a queued row: the sample bits in the narrowest word that holds them
-template <int RB>
-struct JsfsQ {
-    using T = uint32_t;
-    __device__ __forceinline__ static T put(uint64_t t) { return (uint32_t)t; }
-    __device__ __forceinline__ static uint64_t get(T q) { return q; }
-};
-template <>
-struct JsfsQ<8> {
-    using T = uint64_t;
-    __device__ __forceinline__ static T put(uint64_t t) { return t; }
-    __device__ __forceinline__ static uint64_t get(T q) { return q; }
-};
-template <>
-struct JsfsQ<16> {
-    using T = M2;
-    __device__ __forceinline__ static T put(M2 t) { return t; }
-    __device__ __forceinline__ static M2 get(T q) { return q; }
-};
-
-// LDS written by some lanes of a wave, read by others of the same wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ long long wave_sum_i64(long long v) {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
@@ -64,7 +35,7 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
 // Hudson's estimator as a ratio of sums (include/popbam_gpu.h); the unit is built with
 // -ffp-contract=off, so the product and the sums stay separate IEEE operations
 __device__ __forceinline__ double jsfs_fst(long long swi, long long swj, long long sb, int ni, int nj) {
-    if (ni < 2 || nj < 2 || sb == 0) return __longlong_as_double(0x7FF8000000000000LL);
+    if (ni < 2 || nj < 2 || sb == 0) return quiet_nan();
     const double pw_i = (double)swi / (double)(ni * (ni - 1) / 2);
     const double pw_j = (double)swj / (double)(nj * (nj - 1) / 2);
     const double pb = (double)sb / (double)(ni * nj);
@@ -89,40 +60,19 @@ __device__ __forceinline__ void jsfs_sums(const int32_t *h, int cells, int ni, i
 template <int RB>
 __global__ __launch_bounds__(256) void window_jsfs_kernel(DevParams P, const void *__restrict__ rows, uint32_t n_rows,
                                                           uint32_t n_win, JsfsArgs A) {
-    using M = typename RowMask<RB>::T;
-    using Q = JsfsQ<RB>;
-    constexpr int R = 16 / RB;
-    constexpr int QCAP = 64 * R;   // the rows one wave decodes per iteration
+    using Q = QueuedRow<RB>;
     extern __shared__ __align__(16) unsigned char sm[];
     int32_t *s_cells = reinterpret_cast<int32_t *>(sm);
-    __shared__ typename Q::T s_q[4][QCAP];
-    __shared__ uint8_t s_cnt[4][kJsfsCntBytes];
-    __shared__ uint64_t s_pm[PBG_MAX_POPS], s_pmh[PBG_MAX_POPS];
-    __shared__ int32_t s_pn[PBG_MAX_POPS];
+    __shared__ typename Q::T s_q[4][64 * (16 / RB)];
+    __shared__ uint8_t s_cnt[4][kCntBytes];
+    __shared__ PopLds s_pop;
     __shared__ uint32_t s_pw[PBG_MAX_POPS * (PBG_MAX_POPS - 1) / 2];   // the group's pair words
     const int np = P.npops, tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint32_t w = blockIdx.x;
     if (w >= n_win) return;
-    if (tid < np) {
-        s_pm[tid] = P.pop_mask[tid];
-        s_pmh[tid] = P.pop_mask_hi[tid];
-        s_pn[tid] = P.pop_n[tid];
-    }
-    auto pmask = [&](int i) -> M {
-        if constexpr (RB == 16) return M2{s_pm[i], s_pmh[i]};
-        else return s_pm[i];
-    };
-    int64_t wb = A.wins[w].beg, we = A.wins[w].end;
-    if (we <= wb) {
-        wb = we = 0;   // an empty window, whatever its coordinates
-    } else if (wb < 0 || we > (int64_t)n_rows) {
-        // a window outside the rows is reported (pbg_check -> PBG_E_RANGE) and never read
-        if (tid == 0) atomicOr(A.err, 4);
-        wb = we = 0;
-    }
-    const int64_t c0 = wb / R, c1 = (we + R - 1) / R;
-    const int batch = kJsfsCntBytes / np;   // rows whose counts are staged together (>= 16)
-    const int outidx = A.outidx;
+    s_pop.stage(P, tid);
+    const int32_t *s_pn = s_pop.pn;
+    const WindowRows win = clamp_window(A.wins[w], n_rows, A.err, tid);
 
     for (int g = 0; g < A.n_groups; ++g) {
         const int p0 = A.groups[g], p1 = A.groups[g + 1], npg = p1 - p0;
@@ -133,42 +83,9 @@ __global__ __launch_bounds__(256) void window_jsfs_kernel(DevParams P, const voi
         for (int k = tid; k < npg; k += 256) s_pw[k] = A.pairs[p0 + k];   // off the row loop's dependent chain
         __syncthreads();
 
-        // ---- the window's rows: every wave takes 64 words at a time, the next ones loaded ahead
-        uint4 nxt = make_uint4(0, 0, 0, 0);
-        if (c0 + wave * 64 + lane < c1) nxt = load_row_word<RB>(rows, n_rows, c0 + wave * 64 + lane);
-        for (int64_t cb = c0 + wave * 64; cb < c1; cb += 256) {   // wave-uniform
-            const int64_t c = cb + lane;
-            const uint4 q = nxt;
-            nxt = c + 256 < c1 ? load_row_word<RB>(rows, n_rows, c + 256) : make_uint4(0, 0, 0, 0);
-            M t[R];
-            uint32_t vm = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int64_t ri = c * R + r;
-                bool cnt, sg;
-                row_in_word<RB>(q, r, t[r], cnt, sg);
-                vm |= (c < c1 && ri >= wb && ri < we && sg) ? (1u << r) : 0u;
-            }
-            const uint32_t ls = (uint32_t)__popc(vm);
-            const uint32_t incl = wave_incl_scan_s(ls);
-            uint32_t j = incl - ls;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if ((vm >> r) & 1u) s_q[wave][j++] = Q::put(t[r]);
-            const int nq = __builtin_amdgcn_readlane((int)incl, 63);
-            if (nq == 0) continue;
-            wave_sync();
-            for (int b0 = 0; b0 < nq; b0 += batch) {
-                const int nb = nq - b0 < batch ? nq - b0 : batch;
-                // (row, population): each count once, flipped when the outgroup is derived
-                for (int k = lane; k < nb * np; k += 64) {
-                    const int row = k / np, i = k - row * np;
-                    const M tt = Q::get(s_q[wave][b0 + row]);
-                    int f = (int)pc(tt & pmask(i));
-                    if (outidx >= 0 && bit(tt, outidx)) f = s_pn[i] - f;
-                    s_cnt[wave][k] = (uint8_t)f;
-                }
-                wave_sync();
+        // ---- the window's rows (pbg_rows.h): one word loaded ahead
+        stream_window_rows<RB, 1>(rows, n_rows, win, wave, lane, s_q[wave], [&](int nq) {
+            count_batches<RB>(s_q[wave], nq, s_pop, np, A.outidx, lane, s_cnt[wave], [&](int nb) {
                 // (row, pair of this group): one cell each
                 for (int k = lane; k < nb * npg; k += 64) {
                     const int row = k / npg, pr = k - row * npg;
@@ -178,9 +95,8 @@ __global__ __launch_bounds__(256) void window_jsfs_kernel(DevParams P, const voi
                     const int idx = (int)(pw & 0x7FFFu) - base + a * (s_pn[jj] + 1) + b;
                     if ((uint32_t)idx < (uint32_t)ncell) atomicAdd(&s_cells[idx], 1);
                 }
-                wave_sync();   // the next batch's counts, the next iteration's queue
-            }
-        }
+            });
+        });
         __syncthreads();
 
         // ---- the group's results
@@ -217,22 +133,14 @@ __global__ __launch_bounds__(256) void window_jsfs_kernel(DevParams P, const voi
     }
 }
 
-template __global__ void window_jsfs_kernel<2>(DevParams, const void *, uint32_t, uint32_t, JsfsArgs);
-template __global__ void window_jsfs_kernel<4>(DevParams, const void *, uint32_t, uint32_t, JsfsArgs);
-template __global__ void window_jsfs_kernel<8>(DevParams, const void *, uint32_t, uint32_t, JsfsArgs);
-template __global__ void window_jsfs_kernel<16>(DevParams, const void *, uint32_t, uint32_t, JsfsArgs);
-
 hipError_t launch_window_jsfs(int rb, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                               const JsfsArgs &A, hipStream_t stream) {
     if (n_win == 0 || A.n_pairs == 0) return hipSuccess;
     const dim3 g(n_win), b(256);
     const size_t lds = (size_t)A.lds_cells * 4;
-    switch (rb) {
-        case 2: hipLaunchKernelGGL(window_jsfs_kernel<2>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-        case 4: hipLaunchKernelGGL(window_jsfs_kernel<4>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-        case 8: hipLaunchKernelGGL(window_jsfs_kernel<8>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-        default: hipLaunchKernelGGL(window_jsfs_kernel<16>, g, b, lds, stream, P, rows, n_rows, n_win, A); break;
-    }
+    dispatch_rb(rb, [&](auto RB) {
+        hipLaunchKernelGGL(window_jsfs_kernel<decltype(RB)::value>, g, b, lds, stream, P, rows, n_rows, n_win, A);
+    });
     return hipGetLastError();
 }
 

@@ -339,7 +339,6 @@ struct DecayArgs {
 // groups of consecutive pairs whose cells fit kJsfsLdsCells (one pair is at most 64 * 64 = 4,096
 // cells), the window's rows streamed once per group.
 constexpr int kJsfsLdsCells = 8192;   // 32 KiB of histogram per workgroup (beside 21.3 KiB static)
-constexpr int kJsfsCntBytes = 1024;   // per wave: the staged per-population counts of a batch of rows
 // pair p of the context: off[p] | i << 15 | j << 21 (off < 17,767 < 2^15; i, j < 64)
 __host__ __device__ inline uint32_t jsfs_pair_word(uint32_t off, int i, int j) { return off | (uint32_t)i << 15 | (uint32_t)j << 21; }
 struct JsfsArgs {
@@ -360,7 +359,6 @@ struct JsfsArgs {
 // is conflict-free); lists longer than kDstatLdsTriples go in groups of that many consecutive
 // triples, the window's rows streamed once per group.
 constexpr int kDstatLdsTriples = 512;    // 24 KiB of sums per workgroup at most (beside 15.3 KiB static)
-constexpr int kDstatCntBytes = 1024;     // per wave: the staged per-population counts of a batch of rows
 constexpr int kDstatLaneTriples = 64;    // lists up to this long: a lane keeps one triple's sums in registers
 // triple (p1, p2, p3) of the call's list: p1 | p2 << 6 | p3 << 12 (populations < 64)
 __host__ __device__ inline uint32_t dstat_triple_word(int p1, int p2, int p3) {

@@ -37,23 +37,20 @@ struct WinList {                         // a device window list, kept by conten
     uint32_t dsites, n_win;
     pbg_window *d = nullptr;
 };
+struct DevBuf {                          // a device buffer that only grows (stream.cpp: grow)
+    void *d = nullptr;
+    size_t cap = 0;                      // bytes; 0 whenever d is null
+};
 struct StreamBufs {
     hipStream_t copy = nullptr, comp = nullptr;
     StreamSlot slot[2];
-    void *d_rows = nullptr;
-    size_t rows_cap = 0;
-    uint64_t *d_cb = nullptr;
-    size_t cb_cap = 0;
-    void *d_out = nullptr;               // window outputs of one command
-    size_t out_cap = 0;
-    void *d_decay = nullptr;             // ld --decay: pairs | r2_sum of one command
-    size_t decay_cap = 0;
-    void *d_jsfs = nullptr;              // sfs --joint: cells | fst of one block of windows
-    size_t jsfs_cap = 0;
-    void *d_dstat = nullptr;             // sfs --dstat: sums | d | fd | fdm of one block of windows
-    size_t dstat_cap = 0;
-    void *d_hfs = nullptr;               // haplo --hfs: h | counts | k of one block of windows
-    size_t hfs_cap = 0;
+    DevBuf rows;                         // the region's packed rows
+    DevBuf cb;                           // snp -o 0: the region's consensus words
+    DevBuf out;                          // window outputs of one command
+    DevBuf decay;                        // ld --decay: pairs | r2_sum of one command
+    DevBuf jsfs;                         // sfs --joint: cells | fst of one block of windows
+    DevBuf dstat;                        // sfs --dstat: sums | d | fd | fdm of one block of windows
+    DevBuf hfs;                          // haplo --hfs: h | counts | k of one block of windows
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };

@@ -1,6 +1,11 @@
-// pbg_rows.h -- device helpers shared by the statistics kernels (stats_kernel.hip,
-// decay_kernel.hip): the sample-mask types, the packed-row decoder and the wave prefix sum.
+// pbg_rows.h -- device helpers shared by the kernels that read packed rows.  For all of them
+// (stats_kernel.hip, decay_kernel.hip and the three below): the sample-mask types, the packed-row
+// decoder and the wave prefix sum.  For the side-table kernels (jsfs_kernel.hip, dstat_kernel.hip,
+// hfs_kernel.hip): the window clamp, the row stream that feeds a wave's LDS queue, the per-population
+// count batches of jsfs and dstat, and the launch switch over the row width.
 #pragma once
+#include <type_traits>
+
 #include "pbg_common.h"
 
 namespace pbg {
@@ -104,6 +109,160 @@ __device__ __forceinline__ uint32_t compact32(M2 t, M2 pm) {
     return lo | pext32(t.hi, pm.hi, k);
 }
 
+// ---- the row stream of the side-table kernels (jsfs_kernel.hip, dstat_kernel.hip, hfs_kernel.hip)
+//
+// One workgroup of four waves per window.  Every wave takes 64 consecutive 16-byte row words of the
+// window at a time (wave v the words v * 64 .., then 256 words on), the next AHEAD words of each
+// lane loaded ahead; it decodes them, packs the segregating rows of the window into an LDS queue
+// of its own (wave prefix sum, so the queue keeps the rows' order) and hands the queue to the
+// caller's body.  No list of rows outlives a trip, so there is no capacity and no workspace: a trip
+// decodes at most 64 * (16 / RB) rows, which is the queue's size.
+
+// LDS written by some lanes of a wave, read by others of the same wave
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
+
+// a queued row: the sample bits in the narrowest word that holds them
+template <int RB>
+struct QueuedRow {
+    using T = uint32_t;
+    __device__ __forceinline__ static T put(uint64_t t) { return (uint32_t)t; }
+    __device__ __forceinline__ static uint64_t get(T q) { return q; }
+};
+template <>
+struct QueuedRow<8> {
+    using T = uint64_t;
+    __device__ __forceinline__ static T put(uint64_t t) { return t; }
+    __device__ __forceinline__ static uint64_t get(T q) { return q; }
+};
+template <>
+struct QueuedRow<16> {
+    using T = M2;
+    __device__ __forceinline__ static T put(M2 t) { return t; }
+    __device__ __forceinline__ static M2 get(T q) { return q; }
+};
+
+// the populations' masks and sizes in LDS; stage() is followed by a __syncthreads() of the caller's
+struct PopLds {
+    uint64_t pm[PBG_MAX_POPS], pmh[PBG_MAX_POPS];
+    int32_t pn[PBG_MAX_POPS];
+    __device__ __forceinline__ void stage(const DevParams &P, int tid) {
+        if (tid < P.npops) {
+            pm[tid] = P.pop_mask[tid];
+            pmh[tid] = P.pop_mask_hi[tid];
+            pn[tid] = P.pop_n[tid];
+        }
+    }
+    template <int RB>
+    __device__ __forceinline__ typename RowMask<RB>::T mask(int i) const {
+        if constexpr (RB == 16) return M2{pm[i], pmh[i]};
+        else return pm[i];
+    }
+};
+
+// the rows [wb, we) of a window: end <= beg is an empty window, whatever its coordinates; a window
+// outside the rows is empty too, reported (error bit 4: pbg_check -> PBG_E_RANGE) and never read
+struct WindowRows {
+    int64_t wb, we;
+    bool empty;
+};
+__device__ __forceinline__ WindowRows clamp_window(const pbg_window &win, uint32_t n_rows, int *err, int tid) {
+    const int64_t wb = win.beg, we = win.end;
+    if (we > wb && wb >= 0 && we <= (int64_t)n_rows) return {wb, we, false};
+    if (we > wb && tid == 0) atomicOr(err, 4);
+    return {0, 0, true};
+}
+
+// The stream.  q is the calling wave's queue of 64 * (16 / RB) entries.  body(nq) runs once per
+// trip that queued nq > 0 rows, q[0 .. nq) visible to every lane of the wave, and may use wave-level
+// barriers: the trip count and nq are wave-uniform.  A lane past the window's last word (c >= c1)
+// decodes a zero word it never loaded; the last word is loaded row by row (load_row_word).
+template <int RB, int AHEAD, class Body>
+__device__ __forceinline__ void stream_window_rows(const void *rows, uint32_t n_rows, const WindowRows &win, int wave,
+                                                   int lane, typename QueuedRow<RB>::T *q, Body body) {
+    using Q = QueuedRow<RB>;
+    constexpr int R = 16 / RB;
+    const int64_t wb = win.wb, we = win.we, c0 = wb / R, c1 = (we + R - 1) / R;
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    uint4 nx[AHEAD];
+#pragma unroll
+    for (int a = 0; a < AHEAD; ++a) {
+        const int64_t c = c0 + wave * 64 + lane + 256 * a;
+        nx[a] = c < c1 ? load_row_word<RB>(rows, n_rows, c) : zero;
+    }
+    for (int64_t cb = c0 + wave * 64; cb < c1; cb += 256) {   // wave-uniform
+        const int64_t c = cb + lane;
+        const uint4 w = nx[0];
+        // this trip's word has arrived before the next load is issued.  Left to the compiler the wait
+        // goes where the word is first used, which may be after the issue, and a wait there covers the
+        // new load too (the loads are conditional, so it is vmcnt(0)) and undoes the load-ahead
+        __builtin_amdgcn_s_waitcnt(0);
+#pragma unroll
+        for (int a = 1; a < AHEAD; ++a) nx[a - 1] = nx[a];
+        nx[AHEAD - 1] = c + 256 * AHEAD < c1 ? load_row_word<RB>(rows, n_rows, c + 256 * AHEAD) : zero;
+        typename RowMask<RB>::T t[R];
+        uint32_t vm = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t ri = c * R + r;
+            bool cnt, sg;
+            row_in_word<RB>(w, r, t[r], cnt, sg);
+            vm |= (c < c1 && ri >= wb && ri < we && sg) ? (1u << r) : 0u;
+        }
+        const uint32_t ls = (uint32_t)__popc(vm);
+        const uint32_t incl = wave_incl_scan_s(ls);
+        uint32_t j = incl - ls;   // j + ls <= incl of lane 63 <= 64 * R
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if ((vm >> r) & 1u) q[j++] = Q::put(t[r]);
+        const int nq = __builtin_amdgcn_readlane((int)incl, 63);
+        if (nq == 0) continue;
+        wave_sync();
+        body(nq);
+        wave_sync();   // the next trip's queue
+    }
+}
+
+// jsfs and dstat: the per-population counts of the queued rows, kCntBytes / n_pops rows (>= 16) at
+// a time.  Per batch, (row, population) items form each count once -- popcount within the mask,
+// flipped (n - count) when the outgroup carries the derived allele -- and park it as a byte at
+// cnt[row * n_pops + population]; then every lane of the wave runs batch(nb) over the nb rows' bytes.
+constexpr int kCntBytes = 1024;   // per wave
+template <int RB, class Batch>
+__device__ __forceinline__ void count_batches(const typename QueuedRow<RB>::T *q, int nq, const PopLds &pops, int np,
+                                              int outidx, int lane, uint8_t *cnt, Batch batch) {
+    const int rows_per = kCntBytes / np;
+    for (int b0 = 0; b0 < nq; b0 += rows_per) {
+        if (b0) wave_sync();   // the previous batch's readers
+        const int nb = nq - b0 < rows_per ? nq - b0 : rows_per;
+        for (int k = lane; k < nb * np; k += 64) {
+            const int row = k / np, i = k - row * np;
+            const auto tt = QueuedRow<RB>::get(q[b0 + row]);
+            int f = (int)pc(tt & pops.mask<RB>(i));
+            if (outidx >= 0 && bit(tt, outidx)) f = pops.pn[i] - f;
+            cnt[k] = (uint8_t)f;
+        }
+        wave_sync();
+        batch(nb);
+    }
+}
+
 }  // namespace
+
+// launches f with the row width as a compile-time constant: f(std::integral_constant<int, RB>)
+template <class F>
+void dispatch_rb(int rb, F f) {
+    switch (rb) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
 
 }  // namespace pbg

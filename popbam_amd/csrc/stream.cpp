@@ -165,6 +165,51 @@ int ensure_slot(pbg_ctx *c, pbg::StreamSlot &s, uint32_t chunk, size_t keys) {
     return PBG_OK;
 }
 
+// at least `bytes` of device memory in b.  A buffer that is too small is freed first (hipFree waits
+// for the device, so no launch still reads it); a failed allocation leaves it empty
+int grow(pbg_ctx *c, pbg::DevBuf &b, size_t bytes) {
+    if (b.d && b.cap >= bytes) return PBG_OK;
+    if (b.d) HIPCHK(c, hipFree(b.d));
+    b = pbg::DevBuf{};
+    HIPCHK(c, hipMalloc(&b.d, bytes));
+    b.cap = bytes;
+    return PBG_OK;
+}
+
+// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs) is computed and copied to the host
+// a block of windows at a time, so that its device buffer and its host copy stay at kStage bytes each
+// however many windows and populations there are.
+constexpr size_t kStage = 64u << 20;
+struct D2H {
+    void *dst;
+    const void *src;
+    size_t bytes;
+};
+struct WinBlocks {
+    uint32_t size = 0;         // windows per block (0: the command has no such table)
+    uint32_t w0 = 0, w1 = 0;   // the windows of the block on the host
+};
+WinBlocks win_blocks(bool on, uint32_t nw, size_t bytes_per_window) {
+    WinBlocks b;
+    if (on) b.size = (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kStage / bytes_per_window));
+    return b;
+}
+// the block that starts at window `first` to the host: call(first, cnt, copies) sizes the table's
+// buffers for b.size windows, runs its kernel over cnt windows and names the copies of their results
+template <class Call>
+int next_block(pbg_ctx *c, hipStream_t s, WinBlocks &b, uint32_t first, uint32_t nw, Call call) {
+    const uint32_t cnt = std::min(b.size, nw - first);
+    std::vector<D2H> copies;
+    int rc = call(first, cnt, copies);
+    if (rc) return rc;
+    if ((rc = pbg_check(c, s))) return rc;
+    for (const D2H &x : copies) HIPCHK(c, hipMemcpyAsync(x.dst, x.src, x.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    b.w0 = first;
+    b.w1 = first + cnt;
+    return PBG_OK;
+}
+
 // a pair of timing events from the context's pool
 int ev_pair(pbg_stream *st, int kind, hipEvent_t &a, hipEvent_t &b) {
     pbg_ctx *c = st->c;
@@ -316,13 +361,8 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
     const size_t b_ns = al(szw * 4), b_seg = al(szw * 4), b_d1 = al(n_d1 * 8), b_d2 = al(n_d2 * 8), b_d3 = al(n_d3 * 8),
                  b_i1 = al(szp * 4), b_i2 = al(szp * 4), b_i3 = al(szq * 4), b_td = al(szt * 4), b_bins = al(szb * 4);
     const size_t need = b_ns + b_seg + b_d1 + b_d2 + b_d3 + b_i1 + b_i2 + b_i3 + b_td + b_bins;
-    if (c->sb.out_cap < need) {
-        if (c->sb.d_out) HIPCHK(c, hipFree(c->sb.d_out));
-        c->sb.d_out = nullptr;
-        HIPCHK(c, hipMalloc(&c->sb.d_out, need));
-        c->sb.out_cap = need;
-    }
-    char *o = (char *)c->sb.d_out;
+    if ((rc = grow(c, c->sb.out, need))) return rc;
+    char *o = (char *)c->sb.out.d;
     int32_t *o_ns = (int32_t *)o;                o += b_ns;
     int32_t *o_seg = (int32_t *)o;               o += b_seg;
     double *d1 = (double *)o;                    o += b_d1;
@@ -373,15 +413,9 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
     std::vector<double> h_dsum;
     if (decay) {
         const size_t szk = szp * (size_t)std::max(cmd->decay_bins, 0);
-        if (c->sb.decay_cap < szk * 16 + 16) {
-            if (c->sb.d_decay) HIPCHK(c, hipFree(c->sb.d_decay));
-            c->sb.d_decay = nullptr;
-            c->sb.decay_cap = 0;
-            HIPCHK(c, hipMalloc(&c->sb.d_decay, szk * 16 + 16));
-            c->sb.decay_cap = szk * 16 + 16;
-        }
+        if ((rc = grow(c, c->sb.decay, szk * 16 + 16))) return rc;
         const pbg_decay_opts dopt{cmd->decay_bin, cmd->decay_bins, cmd->min_freq, 0};
-        const pbg_decay_out dout{(int64_t *)c->sb.d_decay, (double *)c->sb.d_decay + szk, nullptr};
+        const pbg_decay_out dout{(int64_t *)c->sb.decay.d, (double *)c->sb.decay.d + szk, nullptr};
         if ((rc = pbg_window_ld_decay(c, d_rows, dsites, d_win, nw, &dopt, &dout, s))) return rc;
         if ((rc = pbg_check(c, s))) return rc;
         h_dpairs.resize(szk);
@@ -391,117 +425,67 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
     }
     HIPCHK(c, hipStreamSynchronize(s));
     // sfs --joint: the joint-spectrum kernel over the same windows (its columns follow the
-    // reference's and --theta's), a block of windows at a time so that the device and the host copy
-    // of the cells stay at kJsfsStage bytes each however many windows and populations there are
+    // reference's and --theta's)
     const bool joint = stats == PBG_S_SFS && (cmd->output & 2) && np > 1;
     const size_t jC = joint ? (size_t)pbg_jsfs_cells(c) : 0, jP = (size_t)np * (np - 1) / 2;
-    constexpr size_t kJsfsStage = 64u << 20;
-    const uint32_t jblock = joint ? (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kJsfsStage / (jC * 4 + jP * 8))) : 0;
+    WinBlocks jw = win_blocks(joint, nw, jC * 4 + jP * 8);
     std::vector<int32_t> h_jcells;
     std::vector<double> h_jfst;
-    uint32_t j0 = 0, j1 = 0;   // the windows of the block on the host
-    auto joint_block = [&](uint32_t first) -> int {
-        const uint32_t cnt = std::min(jblock, nw - first);
-        const size_t b_cells = al((size_t)jblock * jC * 4), need_j = b_cells + (size_t)jblock * jP * 8;
-        if (c->sb.jsfs_cap < need_j) {
-            if (c->sb.d_jsfs) HIPCHK(c, hipFree(c->sb.d_jsfs));
-            c->sb.d_jsfs = nullptr;
-            c->sb.jsfs_cap = 0;
-            HIPCHK(c, hipMalloc(&c->sb.d_jsfs, need_j));
-            c->sb.jsfs_cap = need_j;
-        }
-        const pbg_jsfs_opts jopt{cmd->outidx, 0};
-        const pbg_jsfs_out jout{(int32_t *)c->sb.d_jsfs, nullptr, (double *)((char *)c->sb.d_jsfs + b_cells)};
-        int jrc = pbg_window_jsfs(c, d_rows, dsites, d_win + first, cnt, &jopt, &jout, s);
+    auto joint_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t b_cells = al((size_t)jw.size * jC * 4);
+        const int jrc = grow(c, c->sb.jsfs, b_cells + (size_t)jw.size * jP * 8);
         if (jrc) return jrc;
-        if ((jrc = pbg_check(c, s))) return jrc;
+        const pbg_jsfs_opts jopt{cmd->outidx, 0};
+        const pbg_jsfs_out jout{(int32_t *)c->sb.jsfs.d, nullptr, (double *)((char *)c->sb.jsfs.d + b_cells)};
         h_jcells.resize((size_t)cnt * jC);
         h_jfst.resize((size_t)cnt * jP);
-        HIPCHK(c, d2h(h_jcells.data(), jout.cells, h_jcells.size() * 4));
-        HIPCHK(c, d2h(h_jfst.data(), jout.fst, h_jfst.size() * 8));
-        HIPCHK(c, hipStreamSynchronize(s));
-        j0 = first;
-        j1 = first + cnt;
-        return PBG_OK;
+        copies = {{h_jcells.data(), jout.cells, h_jcells.size() * 4}, {h_jfst.data(), jout.fst, h_jfst.size() * 8}};
+        return pbg_window_jsfs(c, d_rows, dsites, d_win + first, cnt, &jopt, &jout, s);
     };
     // sfs --dstat: the D-statistic kernel over the same windows and all triples of the populations
-    // (its columns follow --joint's), in blocks of windows of at most kDstatStage bytes
+    // (its columns follow --joint's)
     const bool dstat = stats == PBG_S_SFS && (cmd->output & 4) && np > 2;
     const std::vector<pbg_triple> dtr = dstat ? pbg::dstat_triples(np) : std::vector<pbg_triple>();
     const size_t dT = dtr.size();
     if (dT > PBG_DSTAT_MAX_TRIPLES) return fail(c, PBG_E_ARG, "Too many populations for --dstat");
-    constexpr size_t kDstatStage = 64u << 20;
-    const uint32_t dblock = dstat ? (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kDstatStage / (dT * 72))) : 0;
+    WinBlocks dw = win_blocks(dstat, nw, dT * 72);
     std::vector<int64_t> h_dsums;
     std::vector<double> h_dd, h_dfd, h_dfdm;
-    uint32_t k0 = 0, k1 = 0;   // the windows of the block on the host
-    auto dstat_block = [&](uint32_t first) -> int {
-        const uint32_t cnt = std::min(dblock, nw - first);
-        const size_t per = (size_t)dblock * dT, need_d = per * 72;
-        if (c->sb.dstat_cap < need_d) {
-            if (c->sb.d_dstat) HIPCHK(c, hipFree(c->sb.d_dstat));
-            c->sb.d_dstat = nullptr;
-            c->sb.dstat_cap = 0;
-            HIPCHK(c, hipMalloc(&c->sb.d_dstat, need_d));
-            c->sb.dstat_cap = need_d;
-        }
+    auto dstat_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t per = (size_t)dw.size * dT, got = (size_t)cnt * dT;
+        const int drc = grow(c, c->sb.dstat, per * 72);
+        if (drc) return drc;
         const pbg_dstat_opts dopt{cmd->outidx, (int32_t)dT, dtr.data()};
-        int64_t *d_sums = (int64_t *)c->sb.d_dstat;
+        int64_t *d_sums = (int64_t *)c->sb.dstat.d;
         double *d_val = (double *)(d_sums + per * 6);
         const pbg_dstat_out dout{d_sums, d_val, d_val + per, d_val + 2 * per};
-        int drc = pbg_window_dstat(c, d_rows, dsites, d_win + first, cnt, &dopt, &dout, s);
-        if (drc) return drc;
-        if ((drc = pbg_check(c, s))) return drc;
-        const size_t got = (size_t)cnt * dT;
         h_dsums.resize(got * 6);
         h_dd.resize(got);
         h_dfd.resize(got);
         h_dfdm.resize(got);
-        HIPCHK(c, d2h(h_dsums.data(), dout.sums, got * 48));
-        HIPCHK(c, d2h(h_dd.data(), dout.d, got * 8));
-        HIPCHK(c, d2h(h_dfd.data(), dout.fd, got * 8));
-        HIPCHK(c, d2h(h_dfdm.data(), dout.fdm, got * 8));
-        HIPCHK(c, hipStreamSynchronize(s));
-        k0 = first;
-        k1 = first + cnt;
-        return PBG_OK;
+        copies = {{h_dsums.data(), dout.sums, got * 48}, {h_dd.data(), dout.d, got * 8}, {h_dfd.data(), dout.fd, got * 8},
+                  {h_dfdm.data(), dout.fdm, got * 8}};
+        return pbg_window_dstat(c, d_rows, dsites, d_win + first, cnt, &dopt, &dout, s);
     };
     // haplo --hfs: the haplotype-spectrum kernel over the same windows (its columns follow the
-    // reference's), in blocks of windows of at most kHfsStage bytes
+    // reference's)
     const bool hfs = cmd->cmd == PBG_CMD_HAPLO && cmd->hfs != 0;
     const size_t hS = (size_t)pbg_hfs_stride(c), hper = (size_t)np * (hS * 4 + 4 + 40);   // bytes per window
-    constexpr size_t kHfsStage = 64u << 20;
-    const uint32_t hblock = hfs ? (uint32_t)std::max<size_t>(1, std::min<size_t>(nw, kHfsStage / hper)) : 0;
+    WinBlocks hw = win_blocks(hfs, nw, hper);
     std::vector<double> h_hh;
     std::vector<int32_t> h_hcounts, h_hk;
-    uint32_t m0 = 0, m1 = 0;   // the windows of the block on the host
-    auto hfs_block = [&](uint32_t first) -> int {
-        const uint32_t cnt = std::min(hblock, nw - first);
-        const size_t per = (size_t)hblock * np, need_h = per * (hS * 4 + 4 + 40);
-        if (c->sb.hfs_cap < need_h) {
-            if (c->sb.d_hfs) HIPCHK(c, hipFree(c->sb.d_hfs));
-            c->sb.d_hfs = nullptr;
-            c->sb.hfs_cap = 0;
-            HIPCHK(c, hipMalloc(&c->sb.d_hfs, need_h));
-            c->sb.hfs_cap = need_h;
-        }
-        double *d_h = (double *)c->sb.d_hfs;
+    auto hfs_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t per = (size_t)hw.size * np, got = (size_t)cnt * np;
+        const int hrc = grow(c, c->sb.hfs, hw.size * hper);
+        if (hrc) return hrc;
+        double *d_h = (double *)c->sb.hfs.d;
         int32_t *d_counts = (int32_t *)(d_h + per * 5), *d_k = d_counts + per * hS;
         const pbg_hfs_out hout{d_k, d_counts, nullptr, nullptr, d_h};
-        int hrc = pbg_window_hfs(c, d_rows, dsites, d_win + first, cnt, &hout, s);
-        if (hrc) return hrc;
-        if ((hrc = pbg_check(c, s))) return hrc;
-        const size_t got = (size_t)cnt * np;
         h_hh.resize(got * 5);
         h_hcounts.resize(got * hS);
         h_hk.resize(got);
-        HIPCHK(c, d2h(h_hh.data(), d_h, got * 40));
-        HIPCHK(c, d2h(h_hcounts.data(), d_counts, got * hS * 4));
-        HIPCHK(c, d2h(h_hk.data(), d_k, got * 4));
-        HIPCHK(c, hipStreamSynchronize(s));
-        m0 = first;
-        m1 = first + cnt;
-        return PBG_OK;
+        copies = {{h_hh.data(), d_h, got * 40}, {h_hcounts.data(), d_counts, got * hS * 4}, {h_hk.data(), d_k, got * 4}};
+        return pbg_window_hfs(c, d_rows, dsites, d_win + first, cnt, &hout, s);
     };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
@@ -510,23 +494,23 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
     };
     for (uint32_t i = 0; i < nw; ++i) {
         if (joint) {
-            if (i >= j1 && (rc = joint_block(i))) return rc;
-            wh.jsfs_fst = slice(h_jfst, (size_t)(i - j0) * jP, jP);
-            wh.jsfs_cells = slice(h_jcells, (size_t)(i - j0) * jC, jC);
+            if (i >= jw.w1 && (rc = next_block(c, s, jw, i, nw, joint_call))) return rc;
+            wh.jsfs_fst = slice(h_jfst, (size_t)(i - jw.w0) * jP, jP);
+            wh.jsfs_cells = slice(h_jcells, (size_t)(i - jw.w0) * jC, jC);
             wh.jsfs_n.assign(c->dp.pop_n, c->dp.pop_n + np);
         }
         if (dstat) {
-            if (i >= k1 && (rc = dstat_block(i))) return rc;
-            wh.dstat_sums = slice(h_dsums, (size_t)(i - k0) * dT * 6, dT * 6);
-            wh.dstat_d = slice(h_dd, (size_t)(i - k0) * dT, dT);
-            wh.dstat_fd = slice(h_dfd, (size_t)(i - k0) * dT, dT);
-            wh.dstat_fdm = slice(h_dfdm, (size_t)(i - k0) * dT, dT);
+            if (i >= dw.w1 && (rc = next_block(c, s, dw, i, nw, dstat_call))) return rc;
+            wh.dstat_sums = slice(h_dsums, (size_t)(i - dw.w0) * dT * 6, dT * 6);
+            wh.dstat_d = slice(h_dd, (size_t)(i - dw.w0) * dT, dT);
+            wh.dstat_fd = slice(h_dfd, (size_t)(i - dw.w0) * dT, dT);
+            wh.dstat_fdm = slice(h_dfdm, (size_t)(i - dw.w0) * dT, dT);
         }
         if (hfs) {
-            if (i >= m1 && (rc = hfs_block(i))) return rc;
-            wh.hfs_h = slice(h_hh, (size_t)(i - m0) * np * 5, (size_t)np * 5);
-            wh.hfs_counts = slice(h_hcounts, (size_t)(i - m0) * np * hS, (size_t)np * hS);
-            wh.hfs_k = slice(h_hk, (size_t)(i - m0) * np, np);
+            if (i >= hw.w1 && (rc = next_block(c, s, hw, i, nw, hfs_call))) return rc;
+            wh.hfs_h = slice(h_hh, (size_t)(i - hw.w0) * np * 5, (size_t)np * 5);
+            wh.hfs_counts = slice(h_hcounts, (size_t)(i - hw.w0) * np * hS, (size_t)np * hS);
+            wh.hfs_k = slice(h_hk, (size_t)(i - hw.w0) * np, np);
             wh.hfs_stride = (int)hS;
         }
         wh.beg = win[i].first;
@@ -575,8 +559,8 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (void *p : {b.d_rows, (void *)b.d_cb, b.d_out, b.d_decay, b.d_jsfs, b.d_dstat, b.d_hfs})
-        if (p) (void)hipFree(p);
+    for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs})
+        if (x->d) (void)hipFree(x->d);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);
     for (auto &e : b.ev) {
@@ -612,27 +596,11 @@ int pbg_stream_open(pbg_ctx *c, const pbg_cmd *cmds, uint32_t n_cmd, int32_t pos
     ch = std::max<uint64_t>(pbg::kSiteBlock, std::min<uint64_t>(ch, std::max<uint32_t>(n_sites, 1)));
     st->chunk = (uint32_t)((ch + pbg::kSiteBlock - 1) / pbg::kSiteBlock * pbg::kSiteBlock);
     const size_t rows_bytes = ((size_t)n_sites * rb + 255) & ~(size_t)255;
-    if (b.rows_cap < rows_bytes || !b.d_rows) {
-        if (b.d_rows) {
-            HIPCHK(c, hipStreamSynchronize(b.comp));
-            HIPCHK(c, hipFree(b.d_rows));
-        }
-        b.d_rows = nullptr;
-        HIPCHK(c, hipMalloc(&b.d_rows, std::max<size_t>(rows_bytes, 256)));
-        b.rows_cap = std::max<size_t>(rows_bytes, 256);
-    }
-    if (n_sites) HIPCHK(c, hipMemsetAsync(b.d_rows, 0, rows_bytes, b.comp));   // unpushed positions: uncounted
+    // an all-empty region still needs one addressable row for the kernels' pointer
+    if (int rc = grow(c, b.rows, std::max<size_t>(rows_bytes, 256))) return rc;
+    if (n_sites) HIPCHK(c, hipMemsetAsync(b.rows.d, 0, rows_bytes, b.comp));   // unpushed positions: uncounted
     if (st->words) {
-        const size_t cbb = (size_t)n_sites * n * 8;
-        if (b.cb_cap < cbb) {
-            if (b.d_cb) {
-                HIPCHK(c, hipStreamSynchronize(b.comp));
-                HIPCHK(c, hipFree(b.d_cb));
-            }
-            b.d_cb = nullptr;
-            HIPCHK(c, hipMalloc((void **)&b.d_cb, cbb + 16));
-            b.cb_cap = cbb;
-        }
+        if (int rc = grow(c, b.cb, (size_t)n_sites * n * 8 + 16)) return rc;
         st->href.assign(n_sites, 0x80);
     }
     *out = st;
@@ -731,7 +699,7 @@ int stream_push(pbg_stream *st, const pbg_pileup *pc, bool compact) {
         c->scan_masked = masked_reference(pc->ref + p0, cl) ? 1 : 0;
         c->scan_compact = compact ? 1 : 0;
         c->cap_hint_keys = (int64_t)(boff[b1] - boff[b0]);
-        rc = pbg_call_sites(c, &dp, (char *)b.d_rows + roff * rb, st->words ? b.d_cb + roff * n : nullptr, b.comp);
+        rc = pbg_call_sites(c, &dp, (char *)b.rows.d + roff * rb, st->words ? (uint64_t *)b.cb.d + roff * n : nullptr, b.comp);
         c->scan_masked = 0;
         c->scan_compact = 0;
         c->cap_hint_keys = -1;
@@ -760,10 +728,9 @@ int stream_finish(pbg_stream *st) {
         HIPCHK(c, hipEventElapsedTime(&ms, b.ev[i].first, b.ev[i].second));
         (st->ev_kind[i] ? st->prof.ms_call : st->prof.ms_h2d) += ms;
     }
-    // an all-empty region still needs one addressable row for the kernels' pointer
     st->text.assign(st->cmds.size(), std::string());
     for (size_t i = 0; i < st->cmds.size(); ++i) {
-        rc = format_command(c, &st->cmds[i], b.d_rows, st->n_sites, st->pos0, st->words ? b.d_cb : nullptr,
+        rc = format_command(c, &st->cmds[i], b.rows.d, st->n_sites, st->pos0, st->words ? (const uint64_t *)b.cb.d : nullptr,
                             st->href.data(), b.comp, st->text[i]);
         if (rc) return st->rc = rc;
     }
@@ -821,7 +788,7 @@ int pbg_stream_rows(const pbg_stream *st, void *dst, size_t cap) {
     if (cap < bytes) return fail(c, PBG_E_RANGE, "rows buffer too small");
     if (!bytes) return PBG_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(dst, c->sb.d_rows, bytes, hipMemcpyDefault, c->sb.comp));
+    HIPCHK(c, hipMemcpyAsync(dst, c->sb.rows.d, bytes, hipMemcpyDefault, c->sb.comp));
     HIPCHK(c, hipStreamSynchronize(c->sb.comp));
     return PBG_OK;
 }

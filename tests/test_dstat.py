@@ -15,11 +15,12 @@ import pytest
 
 import fixtures
 import harness
+from window_helpers import _argv, _arrays, bits, _blocks, mask_words, _native, _pop_masks, popcount, _random_types, _wins_tensor
+from window_helpers import PARTIAL_WORD_CASES, partial_rows
 from popbam_amd import cli
 from popbam_amd import options as opt
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "bin", "popbam")
 BOUNDS_LIB = os.path.join(REPO, "popbam_amd", "variants", "bounds", "libpopbam_gpu.so")
 SEED = 0x15F5
 COUNTED, SEG = 2, 4   # harness flags bits
@@ -28,20 +29,6 @@ NAMES = ("sums", "d", "fd", "fdm")
 
 
 # ---- the checker -----------------------------------------------------------------------
-def popcount(x):
-    """Per-element popcount of a uint64 array."""
-    b = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8).reshape(-1, 8)
-    return np.unpackbits(b, axis=1).sum(axis=1).astype(np.int64)
-
-
-def mask_words(types):
-    """types ([L] u64, or [L, 2] for n > 64) -> (lo, hi) u64 arrays."""
-    types = np.asarray(types, dtype=np.uint64)
-    if types.ndim == 2:
-        return types[:, 0].copy(), types[:, 1].copy()
-    return types, np.zeros(len(types), np.uint64)
-
-
 def all_triples(npop):
     """The command line's list: (i, j, k), i < j, k neither, in lexicographic order."""
     return [(i, j, k) for i in range(npop) for j in range(i + 1, npop) for k in range(npop) if k not in (i, j)]
@@ -102,10 +89,6 @@ def ref_dstat(types, flags, pop_masks, pop_n, wins, triples, outidx=None):
         for t, (p1, p2, p3) in enumerate(tr):
             vals[:, w, t] = ratios_of(sums[w, t], int(nn[p1]), int(nn[p2]), int(nn[p3]))
     return sums, vals[0], vals[1], vals[2]
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
 
 def _assert_same(got, want, what=""):
@@ -180,24 +163,6 @@ def test_checker_on_a_hand_made_window():
     assert np.array_equal(s4[:, 0], s4[:, 2]) and np.array_equal(s4[:, 0], sums[:, 0]) and not np.array_equal(s4[:, 0], s4[:, 1])
 
 
-def _random_types(rng, L, n):
-    if n <= 64:
-        return rng.integers(0, 1 << n, L, dtype=np.uint64)
-    t = np.zeros((L, 2), np.uint64)
-    t[:, 0] = rng.integers(0, 1 << 64, L, dtype=np.uint64)
-    t[:, 1] = rng.integers(0, 1 << (n - 64), L, dtype=np.uint64)
-    return t
-
-
-def _blocks(sizes):
-    """Contiguous population masks of the given sizes."""
-    masks, at = [], 0
-    for s in sizes:
-        masks.append(((1 << s) - 1) << at)
-        at += s
-    return masks
-
-
 @pytest.mark.parametrize("outidx", [None, 0, 16])
 def test_swapping_p1_and_p2(outidx):
     """(P2, P1, P3) against (P1, P2, P3): ABBA <-> BABA, FD2 <-> GD1, FD3 <-> GD3; D changes sign and
@@ -253,10 +218,6 @@ LAYOUTS = ["ref10kb", "overlap", "ragged"]
 _shapes = {}
 
 
-def _pop_masks(params):
-    return ([params.get_pop_mask(i) for i in range(params.n_pops)], [params.pop_n[i] for i in range(params.n_pops)])
-
-
 def _shape(n, npops):
     """One called synthetic batch per shape, shared by the tests (read only), with one context
     without and one with PBG_F_OUTGROUP (the flag is the context's; the rows do not depend on it)."""
@@ -287,21 +248,12 @@ def _layout(name, n_sites):
     return [(int(a), int(b)) for a, b in zip(cuts[:-1], cuts[1:])] + [(5, 5), (0, 1)]
 
 
-def _wins_tensor(wins):
-    import torch
-    return torch.tensor([x for ab in wins for x in ab], dtype=torch.int32).reshape(-1, 2).cuda()
-
-
-def _arrays(x):
-    return tuple(getattr(x, k).cpu().numpy().copy() for k in NAMES)
-
-
 def _run_dstat(ctx, rows, n_rows, wins, triples, outidx=0):
     from popbam_amd import workload
     j = workload.DStat(ctx, len(wins), triples, outidx)
     j(rows, _wins_tensor(wins), n_rows)
     ctx.sync_check()
-    return _arrays(j)
+    return _arrays(j, NAMES)
 
 
 def _outgroup(mode, n):
@@ -391,13 +343,14 @@ def test_dstat_interleaved_masks_and_a_population_of_one(gpu_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [12, 24, 48, 96])
-def test_dstat_partial_last_word(gpu_lib, n):
+@pytest.mark.parametrize("n,words", PARTIAL_WORD_CASES)
+def test_dstat_partial_last_word(gpu_lib, n, words):
     """Windows that end at n_rows = L = 64 * 5 + 3, no multiple of the rows per 16-byte word; the
     rows sit in a larger buffer of 0xFF bytes, which would read as segregating rows with every
-    sample derived."""
+    sample derived.  The same with 513 words and three rows (window_helpers.py): with three
+    populations a full queue of 512 rows is two count batches."""
     import torch
-    L = 64 * 5 + 3
+    L, more = partial_rows(n, words)
     rng = np.random.default_rng(n)
     types = _random_types(rng, L, n)
     flags = np.full(L, COUNTED | SEG, np.uint8)
@@ -406,7 +359,8 @@ def test_dstat_partial_last_word(gpu_lib, n):
     ctx, params, rows = _crafted(n, masks, types, flags)
     big = torch.full((rows.numel() + 4096,), 0xFF, dtype=torch.uint8, device="cuda")
     big[:rows.numel()] = rows
-    wins = [(3, L), (0, L), (L - 1, L)]
+    assert words is None or L == words * (16 // ctx.row_bytes) + 3
+    wins = [(3, L), (0, L), (L - 1, L)] + more
     triples = all_triples(3)
     got = _run_dstat(ctx, big, L, wins, triples)
     _assert_same(got, ref_dstat(types, flags, masks, sizes, wins, triples))
@@ -549,16 +503,16 @@ def test_dstat_interleaves_with_the_other_calls(gpu_lib):
         assert np.array_equal(got[0], alone["zns"][0]) and np.array_equal(got[1], alone["zns"][1])
     same_bytes(arrays(j, JN), alone["jsfs"], JN)
     same_bytes(arrays(d, DN), alone["decay"], DN)
-    same_bytes(_arrays(da), alone["A"], NAMES)
-    same_bytes(_arrays(db), alone["B"], NAMES)
-    same_bytes(_arrays(da2), _arrays(da), NAMES)
+    same_bytes(_arrays(da, NAMES), alone["A"], NAMES)
+    same_bytes(_arrays(db, NAMES), alone["B"], NAMES)
+    same_bytes(_arrays(da2, NAMES), _arrays(da, NAMES), NAMES)
     for k, drop in enumerate(NAMES):   # a NULL member: the others as before, the dropped array untouched
         part = workload.DStat(ctx, len(wins), A)
         getattr(part, drop).fill_(-3)
         setattr(part.out, drop, None)
         part(hp.rows, hp.wins, L)
         ctx.sync_check()
-        got = _arrays(part)
+        got = _arrays(part, NAMES)
         for m, nm in enumerate(NAMES):
             if m == k:
                 assert (got[m] == -3).all(), nm
@@ -584,7 +538,7 @@ def test_dstat_more_lists_than_the_context_keeps(gpu_lib):
         ctx.sync_check()
         for k, (tl, j) in enumerate(zip(lists, runs)):
             idx = [perms.index(t) for t in tl]
-            _assert_same(_arrays(j), tuple(x[:, idx] for x in want), k)
+            _assert_same(_arrays(j, NAMES), tuple(x[:, idx] for x in want), k)
     assert (want[0][0, :, :2] > 0).all()
 
 
@@ -631,19 +585,6 @@ def test_dstat_under_the_bounds_build(gpu_lib, tmp_path):
 
 
 # ---- command lines -----------------------------------------------------------------------
-def _native(argv, timeout=120):
-    e = dict(os.environ)
-    e.pop("WORLD_SIZE", None)
-    r = subprocess.run([BIN, *argv], capture_output=True, timeout=timeout, env=e)
-    return r.returncode, r.stdout.decode(), r.stderr.decode()
-
-
-def _argv(name, cs):
-    d = fixtures.load_case(name)["dir"]
-    a = cs["args"]
-    return [a[0], "-f", os.path.join(d, "ref.fa")] + list(a[1:]) + [os.path.join(d, "in.bam"), cs["region"]]
-
-
 def _split_dstat(ext, pops):
     """The appended --dstat fields of one line -> [(D text, fd text, fdM text, [six sums])] per triple."""
     triples = all_triples(len(pops))

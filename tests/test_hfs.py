@@ -15,11 +15,12 @@ import pytest
 
 import fixtures
 import harness
+from window_helpers import _argv, _arrays, bits, _blocks, _native, _wins_tensor
+from window_helpers import PARTIAL_WORD_CASES, partial_rows
 from popbam_amd import cli
 from popbam_amd import options as opt
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "bin", "popbam")
 BOUNDS_LIB = os.path.join(REPO, "popbam_amd", "variants", "bounds", "libpopbam_gpu.so")
 SEED = 0x4F5
 COUNTED, SEG = 2, 4   # harness flags bits
@@ -102,10 +103,6 @@ def brute_classes(types, flags, members, n, beg, end):
     return sorted((label.count(x) for x in set(label)), reverse=True), label
 
 
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
-
-
 def _assert_same(got, want, what=""):
     for g, w, nm in zip(got, want, NAMES):
         assert g.shape == w.shape and g.dtype == w.dtype, (what, nm, g.shape, w.shape, g.dtype, w.dtype)
@@ -114,15 +111,6 @@ def _assert_same(got, want, what=""):
         else:
             same = g == w
         assert same.all(), (what, nm, np.argwhere(~same)[:5].tolist(), g[~same][:5], w[~same][:5])
-
-
-def _random_types(rng, L, n):
-    if n <= 64:
-        return rng.integers(0, 1 << n, L, dtype=np.uint64)
-    t = np.zeros((L, 2), np.uint64)
-    t[:, 0] = rng.integers(0, 1 << 64, L, dtype=np.uint64)
-    t[:, 1] = rng.integers(0, 1 << (n - 64), L, dtype=np.uint64)
-    return t
 
 
 def _founder_types(rng, L, n, founders):
@@ -136,15 +124,6 @@ def _founder_types(rng, L, n, founders):
         for s in range(n):
             out[r0:r0 + len(sb), s >> 6] |= sb[:, s].astype(np.uint64) << np.uint64(s & 63)
     return out if n > 64 else out[:, 0].copy()
-
-
-def _blocks(sizes):
-    """Contiguous population masks of the given sizes."""
-    masks, at = [], 0
-    for s in sizes:
-        masks.append(((1 << s) - 1) << at)
-        at += s
-    return masks
 
 
 # ---- CPU tests ---------------------------------------------------------------------------
@@ -323,21 +302,12 @@ def _windows(n_sites):
     return wins
 
 
-def _wins_tensor(wins):
-    import torch
-    return torch.tensor([x for ab in wins for x in ab], dtype=torch.int32).reshape(-1, 2).cuda()
-
-
-def _arrays(x):
-    return tuple(getattr(x, k).cpu().numpy().copy() for k in NAMES)
-
-
 def _run_hfs(ctx, rows, n_rows, wins):
     from popbam_amd import workload
     j = workload.Hfs(ctx, len(wins))
     j(rows, _wins_tensor(wins), n_rows)
     ctx.sync_check()
-    return _arrays(j)
+    return _arrays(j, NAMES)
 
 
 @pytest.mark.gpu
@@ -464,22 +434,25 @@ def test_hfs_crafted_rows(gpu_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [12, 24, 48, 96])
-def test_hfs_partial_last_word(gpu_lib, n):
+@pytest.mark.parametrize("n,words", PARTIAL_WORD_CASES)
+def test_hfs_partial_last_word(gpu_lib, n, words):
     """Windows that end at n_rows = L = 64 * 5 + 3, no multiple of the rows per 16-byte word; the rows
-    sit in a larger buffer of 0xFF bytes, which would read as segregating rows with every sample set."""
+    sit in a larger buffer of 0xFF bytes, which would read as segregating rows with every sample set.
+    The same with 513 words and three rows, every row segregating (window_helpers.py)."""
     import torch
-    L = 64 * 5 + 3
+    L, more = partial_rows(n, words)
     rng = np.random.default_rng(n)
     types = _founder_types(rng, L, n, 4)
-    flags = np.where(rng.random(L) < 0.1, COUNTED | SEG, COUNTED).astype(np.uint8)
+    seg = rng.random(L) < 0.1 if words is None else np.ones(L, bool)
+    flags = np.where(seg, COUNTED | SEG, COUNTED).astype(np.uint8)
     flags[L - 1] = COUNTED | SEG
     sizes = [n // 3, n // 3, n - 2 * (n // 3)]
     masks = _blocks(sizes)
     ctx, params, rows = _crafted(n, masks, types, flags)
     big = torch.full((rows.numel() + 4096,), 0xFF, dtype=torch.uint8, device="cuda")
     big[:rows.numel()] = rows
-    wins = [(3, L), (0, L), (L - 1, L), (L - 9, L), (1, 2)]
+    assert words is None or (L == words * (16 // ctx.row_bytes) + 3 and (flags & SEG).all())
+    wins = [(3, L), (0, L), (L - 1, L), (L - 9, L), (1, 2)] + more
     got = _run_hfs(ctx, big, L, wins)
     _assert_same(got, ref_hfs(types, flags, masks, sizes, n, wins))
     assert (got[0][:2] > 1).all()
@@ -603,15 +576,15 @@ def test_hfs_interleaves_with_the_other_calls(gpu_lib):
     same_bytes(arrays(j, JN), alone["jsfs"], JN)
     same_bytes(arrays(d, DN), alone["decay"], DN)
     same_bytes(arrays(t, TN), alone["dstat"], TN)
-    same_bytes(_arrays(h1), alone["hfs"], NAMES)
-    same_bytes(_arrays(h2), _arrays(h1), NAMES)
+    same_bytes(_arrays(h1, NAMES), alone["hfs"], NAMES)
+    same_bytes(_arrays(h2, NAMES), _arrays(h1, NAMES), NAMES)
     for k, drop in enumerate(NAMES):   # a NULL member: the others as before, the dropped array untouched
         part = workload.Hfs(ctx, len(wins))
         getattr(part, drop).fill_(3)
         setattr(part.out, drop, None)
         part(hp.rows, hp.wins, L)
         ctx.sync_check()
-        got = _arrays(part)
+        got = _arrays(part, NAMES)
         for m, nm in enumerate(NAMES):
             if m == k:
                 assert (got[m] == 3).all(), nm
@@ -639,7 +612,7 @@ def test_hfs_agrees_with_calc_nhaps_on_one_population(gpu_lib, n, founders):
     j = workload.Hfs(ctx, len(CROSS_WINS))
     j(rows, wt, CROSS_L)
     ctx.sync_check()
-    k, counts, cls, sums, h = _arrays(j)
+    k, counts, cls, sums, h = _arrays(j, NAMES)
     _assert_same((k, counts, cls, sums, h), ref_hfs(types, flags, [(1 << n) - 1], [n], n, CROSS_WINS))
     nhaps = out.t["nhaps"].cpu().numpy().reshape(-1)
     hap_val = out.t["hap_val"].cpu().numpy().reshape(-1)
@@ -693,23 +666,10 @@ def test_hfs_under_the_bounds_build(gpu_lib, tmp_path, name):
 
 
 # ---- command lines -----------------------------------------------------------------------
-def _native(argv, timeout=120):
-    e = dict(os.environ)
-    e.pop("WORLD_SIZE", None)
-    r = subprocess.run([BIN, *argv], capture_output=True, timeout=timeout, env=e)
-    return r.returncode, r.stdout.decode(), r.stderr.decode()
-
-
 def _haplo_case(name, output):
     args = ["haplo", "-w", "1"] + (["-o", str(output)] if output else [])
     cases = fixtures.load_case(name)["meta"]["cases"]
     return next(cs for cs in cases if cs["args"] == args)
-
-
-def _argv(name, cs):
-    d = fixtures.load_case(name)["dir"]
-    a = cs["args"]
-    return [a[0], "-f", os.path.join(d, "ref.fa")] + list(a[1:]) + [os.path.join(d, "in.bam"), cs["region"]]
 
 
 @pytest.mark.gpu

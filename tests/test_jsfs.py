@@ -15,11 +15,12 @@ import pytest
 
 import fixtures
 import harness
+from window_helpers import _argv, bits, _blocks, mask_words, _native, _pop_masks, popcount, _random_types, _wins_tensor
+from window_helpers import PARTIAL_WORD_CASES, partial_rows
 from popbam_amd import cli
 from popbam_amd import options as opt
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "bin", "popbam")
 BOUNDS_LIB = os.path.join(REPO, "popbam_amd", "variants", "bounds", "libpopbam_gpu.so")
 SEED = 0x15F5
 COUNTED, SEG = 2, 4   # harness flags bits
@@ -27,20 +28,6 @@ F_OUTGROUP = 0x40     # PBG_F_OUTGROUP
 
 
 # ---- the checker -----------------------------------------------------------------------
-def popcount(x):
-    """Per-element popcount of a uint64 array."""
-    b = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8).reshape(-1, 8)
-    return np.unpackbits(b, axis=1).sum(axis=1).astype(np.int64)
-
-
-def mask_words(types):
-    """types ([L] u64, or [L, 2] for n > 64) -> (lo, hi) u64 arrays."""
-    types = np.asarray(types, dtype=np.uint64)
-    if types.ndim == 2:
-        return types[:, 0].copy(), types[:, 1].copy()
-    return types, np.zeros(len(types), np.uint64)
-
-
 def pair_list(npop):
     return [(i, j) for i in range(npop) for j in range(i + 1, npop)]
 
@@ -91,10 +78,6 @@ def ref_jsfs(types, flags, pop_masks, pop_n, wins, outidx=None):
             fst[w, p] = fst_of(*(int(x) for x in diffs[w, p]), ni, nj)
     assert npop == 1 or cells.shape[1] > 0
     return cells, diffs, fst
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
 
 def _assert_same(got, want, what=""):
@@ -172,10 +155,6 @@ LAYOUTS = ["ref10kb", "overlap", "ragged"]
 _shapes = {}
 
 
-def _pop_masks(params):
-    return ([params.get_pop_mask(i) for i in range(params.n_pops)], [params.pop_n[i] for i in range(params.n_pops)])
-
-
 def _shape(n, npops):
     """One called synthetic batch per shape, shared by the tests (read only), with one context
     without and one with PBG_F_OUTGROUP (the flag is the context's; the rows do not depend on it)."""
@@ -204,11 +183,6 @@ def _layout(name, n_sites):
     rng = np.random.default_rng(7)   # test_window_stats_match_oracle's ragged layout
     cuts = np.sort(rng.choice(n_sites, 40, replace=False))
     return [(int(a), int(b)) for a, b in zip(cuts[:-1], cuts[1:])] + [(5, 5), (0, 1)]
-
-
-def _wins_tensor(wins):
-    import torch
-    return torch.tensor([x for ab in wins for x in ab], dtype=torch.int32).reshape(-1, 2).cuda()
 
 
 def _run_jsfs(ctx, rows, n_rows, wins, outidx=0):
@@ -325,24 +299,6 @@ def _crafted(n, masks, types, flags, flag=0):
     return ctx, params, rows
 
 
-def _random_types(rng, L, n):
-    if n <= 64:
-        return rng.integers(0, 1 << n, L, dtype=np.uint64)
-    t = np.zeros((L, 2), np.uint64)
-    t[:, 0] = rng.integers(0, 1 << 64, L, dtype=np.uint64)
-    t[:, 1] = rng.integers(0, 1 << (n - 64), L, dtype=np.uint64)
-    return t
-
-
-def _blocks(sizes):
-    """Contiguous population masks of the given sizes."""
-    masks, at = [], 0
-    for s in sizes:
-        masks.append(((1 << s) - 1) << at)
-        at += s
-    return masks
-
-
 CRAFTED = {"63+63": [63, 63], "120+3+3": [120, 3, 3], "64pops": [2] * 62 + [1, 1]}
 
 
@@ -409,13 +365,13 @@ def test_jsfs_one_population_writes_nothing(gpu_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [12, 24, 48, 96])
-def test_jsfs_partial_last_word(gpu_lib, n):
+@pytest.mark.parametrize("n,words", PARTIAL_WORD_CASES)
+def test_jsfs_partial_last_word(gpu_lib, n, words):
     """Window [3, L) with L = 64 * 5 + 3 rows that ends at n_rows: L is no multiple of the rows per
     16-byte word, and the rows sit in a larger buffer of 0xFF bytes, which would read as segregating
-    rows with every sample derived."""
+    rows with every sample derived.  The same with 513 words and three rows (window_helpers.py)."""
     import torch
-    L = 64 * 5 + 3
+    L, more = partial_rows(n, words)
     rng = np.random.default_rng(n)
     types = _random_types(rng, L, n)
     flags = np.full(L, COUNTED | SEG, np.uint8)
@@ -423,9 +379,10 @@ def test_jsfs_partial_last_word(gpu_lib, n):
     ctx, params, rows = _crafted(n, masks, types, flags)
     big = torch.full((rows.numel() + 4096,), 0xFF, dtype=torch.uint8, device="cuda")
     big[:rows.numel()] = rows
-    wins = [(3, L), (0, L), (L - 1, L)]
+    assert words is None or L == words * (16 // ctx.row_bytes) + 3
+    wins = [(3, L), (0, L), (L - 1, L)] + more
     got = _run_jsfs(ctx, big, L, wins)
-    assert got[0].sum(axis=1).tolist() == [L - 3, L, 1]
+    assert got[0].sum(axis=1).tolist() == [L - 3, L, 1] + [b - a for a, b in more]
     _assert_same(got, ref_jsfs(types, flags, masks, [n // 2, n - n // 2], wins))
     ctx.close()
 
@@ -601,19 +558,6 @@ def test_jsfs_under_the_bounds_build(gpu_lib, tmp_path):
 
 
 # ---- command lines -----------------------------------------------------------------------
-def _native(argv, timeout=120):
-    e = dict(os.environ)
-    e.pop("WORLD_SIZE", None)
-    r = subprocess.run([BIN, *argv], capture_output=True, timeout=timeout, env=e)
-    return r.returncode, r.stdout.decode(), r.stderr.decode()
-
-
-def _argv(name, cs):
-    d = fixtures.load_case(name)["dir"]
-    a = cs["args"]
-    return [a[0], "-f", os.path.join(d, "ref.fa")] + list(a[1:]) + [os.path.join(d, "in.bam"), cs["region"]]
-
-
 def _split_joint(ext, pops):
     """The appended --joint fields of one line -> {(i, j): (fst text, [cells])}."""
     pairs = pair_list(len(pops))

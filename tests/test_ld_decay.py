@@ -15,31 +15,17 @@ import pytest
 
 import fixtures
 import harness
+from window_helpers import bits, mask_words, _native, _pop_masks, popcount, _random_types, _wins_tensor
 from popbam_amd import cli
 from popbam_amd import options as opt
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(REPO, "bin", "popbam")
 BOUNDS_LIB = os.path.join(REPO, "popbam_amd", "variants", "bounds", "libpopbam_gpu.so")
 SEED = 0xDECA7
 COUNTED, SEG = 2, 4   # harness flags bits
 
 
 # ---- the checker -----------------------------------------------------------------------
-def popcount(x):
-    """Per-element popcount of a uint64 array."""
-    b = np.ascontiguousarray(x, dtype=np.uint64).view(np.uint8).reshape(-1, 8)
-    return np.unpackbits(b, axis=1).sum(axis=1).astype(np.int64)
-
-
-def mask_words(types):
-    """types ([L] u64, or [L, 2] for n > 64) -> (lo, hi) u64 arrays."""
-    types = np.asarray(types, dtype=np.uint64)
-    if types.ndim == 2:
-        return types[:, 0].copy(), types[:, 1].copy()
-    return types, np.zeros(len(types), np.uint64)
-
-
 def r2_of(m1, m2, c11, n):
     """The host r^2 table's entry (build_r2_table): plain doubles, x = count / n."""
     x0, x1, x11 = m1 / n, m2 / n, c11 / n
@@ -79,10 +65,6 @@ def ref_decay(types, flags, pop_masks, pop_n, wins, bin_bp, n_bins, min_freq=1):
                 pairs[w, i, kk] = len(vals)
                 r2s[w, i, kk] = np.cumsum(vals)[-1] + 0.0   # a sequential sum from +0.0
     return pairs, r2s, nvar
-
-
-def bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
 
 # ---- CPU tests ---------------------------------------------------------------------------
@@ -131,13 +113,6 @@ def test_decay_option_parses():
         opt.parse_args("ld", ["-f", "ref.fa", "-o", "3", "--decay=5,5", "in.bam", "chr1"])
 
 
-def _native(argv, timeout=120):
-    e = dict(os.environ)
-    e.pop("WORLD_SIZE", None)
-    r = subprocess.run([BIN, *argv], capture_output=True, timeout=timeout, env=e)
-    return r.returncode, r.stdout.decode(), r.stderr.decode()
-
-
 def test_native_decay_errors_match_the_python_cli(capsys):
     d = fixtures.load_case("g01_base")["dir"]
     ref, bam = os.path.join(d, "ref.fa"), os.path.join(d, "in.bam")
@@ -158,10 +133,6 @@ N_SITES = 32_000
 SHAPES = [(12, 2), (24, 3), (48, 2), (96, 4), (40, 1)]   # row widths 2 / 4 / 8 / 16 B; (40, 1): raw one-word masks
 BINS = [(100, 100), (7, 13), (1, 256), (20000, 1)]
 _shapes = {}
-
-
-def _pop_masks(params):
-    return ([params.get_pop_mask(i) for i in range(params.n_pops)], [params.pop_n[i] for i in range(params.n_pops)])
 
 
 def _shape(n, npops):
@@ -190,11 +161,6 @@ def _layout(name, n_sites):
     rng = np.random.default_rng(7)   # test_window_stats_match_oracle's ragged layout
     cuts = np.sort(rng.choice(n_sites, 40, replace=False))
     return [(int(a), int(b)) for a, b in zip(cuts[:-1], cuts[1:])] + [(5, 5), (0, 1)]
-
-
-def _wins_tensor(wins):
-    import torch
-    return torch.tensor([x for ab in wins for x in ab], dtype=torch.int32).reshape(-1, 2).cuda()
 
 
 def _run_decay(ctx, rows, n_rows, wins, bin_bp, n_bins, min_freq=1):
@@ -247,15 +213,6 @@ def _crafted(n, masks, types, flags):
     ctx = _lib.Context(params, 0)
     rows = torch.from_numpy(harness.rows_from_oracle(types, flags, ctx.row_bytes).copy()).cuda()
     return ctx, params, rows
-
-
-def _random_types(rng, L, n):
-    if n <= 64:
-        return rng.integers(0, 1 << n, L, dtype=np.uint64)
-    t = np.zeros((L, 2), np.uint64)
-    t[:, 0] = rng.integers(0, 1 << 64, L, dtype=np.uint64)
-    t[:, 1] = rng.integers(0, 1 << (n - 64), L, dtype=np.uint64)
-    return t
 
 
 @pytest.mark.gpu
