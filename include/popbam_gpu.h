@@ -353,6 +353,41 @@ int pbg_hfs_stride(const pbg_ctx *ctx);   /* the largest population size; 0 for 
 int pbg_window_hfs(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                    uint32_t n_win, const pbg_hfs_out *out, void *stream);
 
+/* Hudson and Kaplan's Rm (1985), the minimum number of recombination events the four-gamete test
+ * implies, and the intervals that witness them, per window and population (an extension; the
+ * reference has no counterpart).  For window [beg, end) and population i (n_i samples, mask pm_i) the
+ * variable sites v_0 < v_1 < ... < v_{V-1} are pbg_window_ld_decay's and ZnS's: the window's rows with
+ * the segregating bit whose m = popcount(types & pm_i) has min_freq <= m <= n_i - min_freq (min_freq 1
+ * or 2, ld -e), in row order.  A site's column is x = types & pm_i; a sample whose bit is clear reads
+ * as ancestral, as calc_zns reads it.  Sites a < b are incompatible when x_a & x_b, x_a & ~x_b & pm_i,
+ * ~x_a & x_b & pm_i and pm_i & ~(x_a | x_b) are all non-zero.  The test is symmetric under
+ * complementing either column, so the outgroup plays no part, and a singleton (m = 1 or n_i - 1) is
+ * never incompatible with anything.  For site b let L(b) be the largest a < b incompatible with b, if
+ * any.  Walk b = 0 .. V-1 with c = 0, the right end of the last chosen interval: when L(b) exists and
+ * L(b) >= c, choose the interval (v_L(b), v_b) and set c = b; two chosen intervals may share an end
+ * site.  Element (w, i) at w * n_pops + i:
+ *   rmin   int32: the number of chosen intervals -- the largest number of pairwise disjoint
+ *          incompatible intervals, which is Hudson and Kaplan's Rm
+ *   n_var  int32: V
+ *   cuts   int32 pairs (left row, right row), absolute row indices, max_cuts pairs per element: the
+ *          first min(rmin, max_cuts) chosen intervals in order, every remaining pair (-1, -1); rmin
+ *          keeps counting past max_cuts
+ * beg >= end, V < 2 and n_i < 4 give rmin = 0; rmin and cuts are the same for min_freq 1 and 2.  A
+ * window outside [0, n_rows] is not read: it gives the empty window's outputs and the next pbg_check
+ * returns PBG_E_RANGE.  A NULL member of pbg_rmin_out is skipped.  Asynchronous; no workspace, no plan
+ * and no list of sites (the walk keeps at most n_i - 3 columns), so a window of any length
+ * works and the call is free to interleave with every other window call on one stream.  Integers only:
+ * two runs give the same bytes.  PBG_E_ARG for a null ctx, rows, wins, opts or out, min_freq not 1 or
+ * 2, max_cuts < 0 and a non-null cuts with max_cuts == 0; n_win == 0 returns PBG_OK. */
+typedef struct { int32_t min_freq, max_cuts; } pbg_rmin_opts;
+typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int32_t *rmin;             /* [n_win * n_pops]                */
+    int32_t *n_var;            /* [n_win * n_pops]                */
+    int32_t *cuts;             /* [n_win * n_pops * max_cuts * 2] */
+} pbg_rmin_out;
+int pbg_window_rmin(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                    uint32_t n_win, const pbg_rmin_opts *opts, const pbg_rmin_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -369,6 +404,8 @@ const char *pbg_build_info(void);
 enum { PBG_CMD_SNP = 0, PBG_CMD_HAPLO = 1, PBG_CMD_DIVERGE = 2, PBG_CMD_TREE = 3,
        PBG_CMD_NUCDIV = 4, PBG_CMD_LD = 5, PBG_CMD_SFS = 6 };   /* popbam_func_t (popbam.h:208) */
 
+enum { PBG_LD_RMIN = 4 };   /* pbg_cmd.output of PBG_CMD_LD: bit 2 */
+
 typedef struct {
     int32_t  cmd;          /* PBG_CMD_*                                                   */
     int32_t  output;       /* -o; sfs: bit 0 = --theta, bit 1 = --joint (a streamed run also runs
@@ -382,7 +419,14 @@ typedef struct {
                               "fd[popI,popJ,popK]:", "fdM[popI,popJ,popK]:" (NA for NaN) and
                               "dsum[popI,popJ,popK]:" the six sums, comma-separated, after
                               --joint's columns; more than PBG_DSTAT_MAX_TRIPLES triples, i.e.
-                              more than 21 populations: PBG_E_ARG)                            */
+                              more than 21 populations: PBG_E_ARG); ld: bits 0-1 = -o (0, 1, 2),
+                              PBG_LD_RMIN = --rmin (a streamed run also runs pbg_window_rmin on the
+                              command's windows with min_freq and appends, per population,
+                              "Rmin[pop]:" the count and "rint[pop]:" the chosen intervals as
+                              left-right in 1-based contig positions, comma-separated (NA when the
+                              count is 0), after the reference's columns and --decay's; they ignore
+                              min_snps).  A bit of `output` and no new field: sizeof(pbg_cmd) stays,
+                              so a program compiled against the header before it keeps running    */
     int32_t  min_sites;    /* -k                                                          */
     int32_t  min_snps;     /* ld -n                                                       */
     int32_t  min_freq;     /* ld 1 / 2 (-e)                                               */
@@ -427,7 +471,8 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
  * prints (+1 applied here).  Same return convention as pbg_run.  It takes no decay arrays and
  * prints the reference's columns only, whatever the command's decay_bin says; no joint-spectrum
  * arrays and no D-statistic arrays either, so sfs output bits 1 (--joint) and 2 (--dstat) add
- * nothing here; no haplotype-spectrum arrays, so haplo's hfs adds nothing here.            */
+ * nothing here; no haplotype-spectrum arrays, so haplo's hfs adds nothing here; no Rmin arrays,
+ * so ld's PBG_LD_RMIN adds nothing here.                                                          */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

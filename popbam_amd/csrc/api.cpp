@@ -103,7 +103,8 @@ int check_outidx(pbg_ctx *c, const char *what, int32_t outidx, int32_t *flip_idx
 }  // namespace
 
 namespace pbg {
-extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat, kBuildKind_hfs;
+extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat, kBuildKind_hfs,
+    kBuildKind_rmin;
 }
 
 namespace {
@@ -485,7 +486,7 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 
 const char *pbg_build_info(void) {
     const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay,
-                               pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat, pbg::kBuildKind_hfs});
+                               pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat, pbg::kBuildKind_hfs, pbg::kBuildKind_rmin});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -875,6 +876,27 @@ int pbg_window_hfs(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wind
     A.sums = out->sums;
     A.h = out->h;
     HIPCHK(c, pbg::launch_window_hfs(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    return PBG_OK;
+}
+
+int pbg_window_rmin(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                    const pbg_rmin_opts *o, const pbg_rmin_out *out, void *stream) {
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    if (o->min_freq != 1 && o->min_freq != 2) return fail(c, PBG_E_ARG, "rmin: min_freq must be 1 or 2");
+    if (o->max_cuts < 0) return fail(c, PBG_E_ARG, "rmin: max_cuts must not be negative");
+    if (out->cuts && o->max_cuts == 0) return fail(c, PBG_E_ARG, "rmin: cuts needs max_cuts of at least 1");
+    if (n_win == 0) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    pbg::RminArgs A{};
+    A.wins = wins;
+    A.err = c->d_err;
+    A.min_freq = o->min_freq;
+    A.max_cuts = o->max_cuts;
+    A.rmin = out->rmin;
+    A.n_var = out->n_var;
+    A.cuts = out->cuts;
+    HIPCHK(c, pbg::launch_window_rmin(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
     return PBG_OK;
 }
 

@@ -319,15 +319,16 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                     }
             }
             break;
-        case PBG_CMD_LD:  // print_ld pop_ld.cpp:650-712
+        case PBG_CMD_LD: {  // print_ld pop_ld.cpp:650-712
+            const int ldo = c.output & 3;   // -o; bit 2 is --rmin
             for (int i = 0; i < np; i++) {
                 o.t("\tS[" + pn(c, i) + "]:\t");
                 o.i(w.ld_snps[i]);
                 const bool sok = w.ld_snps[i] >= c.min_snps;
-                if (c.output == 1) {
+                if (ldo == 1) {
                     o.t("\tomax[" + pn(c, i) + "]:\t");
                     if (sok) o.f(w.ld_val[i]); else o.na();
-                } else if (c.output == 2) {
+                } else if (ldo == 2) {
                     o.t("\tB[" + pn(c, i) + "]:\t");
                     if (sok) o.f(w.ld_val[i]); else o.na();
                     o.t("\tQ[" + pn(c, i) + "]:\t");
@@ -339,7 +340,7 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
             }
             // --decay: per population the bins' mean r^2 and pair counts, appended after the
             // reference's columns (the default output is unchanged); not subject to -n
-            if (c.output == 0 && c.decay_bin > 0 && c.decay_bins > 0 &&
+            if (ldo == 0 && c.decay_bin > 0 && c.decay_bins > 0 &&
                 w.decay_pairs.size() == (size_t)np * c.decay_bins && w.decay_sum.size() == w.decay_pairs.size())
                 for (int i = 0; i < np; i++) {
                     const size_t b0 = (size_t)i * c.decay_bins;
@@ -355,7 +356,24 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                         o.i(w.decay_pairs[b0 + k]);
                     }
                 }
+            // --rmin: per population Hudson and Kaplan's Rm and its intervals as left-right contig
+            // positions, after the reference's columns and --decay's (any -o); not subject to -n
+            if ((c.output & PBG_LD_RMIN) && (int)w.rmin_n.size() == np && w.rmin_cuts.size() == (size_t)np * w.rmin_stride * 2)
+                for (int i = 0; i < np; i++) {
+                    o.t("\tRmin[" + pn(c, i) + "]:\t");
+                    o.i(w.rmin_n[i]);
+                    o.t("\trint[" + pn(c, i) + "]:\t");
+                    if (w.rmin_n[i] <= 0) o.t("NA");
+                    for (int k = 0; k < w.rmin_n[i] && k < w.rmin_stride; k++) {
+                        const size_t at = ((size_t)i * w.rmin_stride + k) * 2;
+                        if (k) o.t(",");
+                        o.i(w.rmin_cuts[at] + 1);
+                        o.t("-");
+                        o.i(w.rmin_cuts[at + 1] + 1);
+                    }
+                }
             break;
+        }
         case PBG_CMD_DIVERGE:  // print_diverge pop_diverge.cpp:496-574
             if (c.output == 0) {
                 for (int i = 0; i < n; i++) {

@@ -389,6 +389,19 @@ struct HfsArgs {
     double *h;                 // [n_win * npops * 5] or null
 };
 
+// window_rmin_kernel (pbg_window_rmin): Hudson and Kaplan's Rm and its intervals per (window,
+// population).  One wave per chain, kRminWaves chains per workgroup; a chain's list of splits lives in
+// registers and its queue of rows in LDS, so there is no workspace.
+constexpr int kRminWaves = 4;
+struct RminArgs {
+    const pbg_window *wins;
+    int *err;
+    int32_t min_freq, max_cuts;
+    int32_t *rmin;             // [n_win * npops] or null
+    int32_t *n_var;            // [n_win * npops] or null
+    int32_t *cuts;             // [n_win * npops * max_cuts * 2] or null
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -534,5 +547,8 @@ hipError_t launch_window_dstat(int row_bytes, const DevParams &P, const void *ro
 // hfs_kernel.hip (static LDS only)
 hipError_t launch_window_hfs(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                              const HfsArgs &A, hipStream_t stream);
+// rmin_kernel.hip (static LDS only)
+hipError_t launch_window_rmin(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                              const RminArgs &A, hipStream_t stream);
 
 }  // namespace pbg

@@ -51,6 +51,7 @@ struct StreamBufs {
     DevBuf jsfs;                         // sfs --joint: cells | fst of one block of windows
     DevBuf dstat;                        // sfs --dstat: sums | d | fd | fdm of one block of windows
     DevBuf hfs;                          // haplo --hfs: h | counts | k of one block of windows
+    DevBuf rmin, rmin_cuts;              // ld --rmin: the counts and the intervals of one block of windows
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };

@@ -51,6 +51,11 @@ struct WindowHost {
     std::vector<double> hfs_h;
     std::vector<int32_t> hfs_k, hfs_counts;
     int hfs_stride = 0;
+    // ld --rmin (PBG_LD_RMIN in pbg_cmd.output): Rm of population p at rmin_n[p] and its chosen intervals as (left,
+    // right) contig positions, 0-based, at [(p * rmin_stride + k) * 2], k < rmin_n[p]
+    // (pbg_window_rmin); empty when the caller has none (pbg_format)
+    std::vector<int32_t> rmin_n, rmin_cuts;
+    int rmin_stride = 0;
 };
 
 // sfs --dstat's triples of n_pops populations: all (i, j, k) with i < j and k neither, in

@@ -2,7 +2,8 @@
 // (stats_kernel.hip, decay_kernel.hip and the three below): the sample-mask types, the packed-row
 // decoder and the wave prefix sum.  For the side-table kernels (jsfs_kernel.hip, dstat_kernel.hip,
 // hfs_kernel.hip): the window clamp, the row stream that feeds a wave's LDS queue, the per-population
-// count batches of jsfs and dstat, and the launch switch over the row width.
+// count batches of jsfs and dstat, and the launch switch over the row width.  For rmin_kernel.hip:
+// the ordered stream of a single wave.
 #pragma once
 #include <type_traits>
 
@@ -225,6 +226,59 @@ __device__ __forceinline__ void stream_window_rows(const void *rows, uint32_t n_
         wave_sync();
         body(nq);
         wave_sync();   // the next trip's queue
+    }
+}
+
+// The ordered stream of one wave (rmin_kernel.hip): the rows of a window in row order, each with its
+// row index.  The stream above deals a window's words to four waves and keeps no index, so it cannot
+// hand one wave a chain in order; here a single wave takes 64 consecutive words at a time, GROUP
+// trips' loads issued together (decay_kernel.hip's gather).  keep(t) decides whether a segregating row
+// of the window is queued and may narrow its bits (it runs once per such row, in no particular
+// order); body(nq) then sees qx[0 .. nq) and qrow[0 .. nq), the kept rows' bits and absolute row
+// indices in row order, under the same rules as above.  A trip queues at most 64 * (16 / RB) rows.
+template <int RB, int GROUP, class Keep, class Body>
+__device__ __forceinline__ void stream_rows_in_order(const void *rows, uint32_t n_rows, const WindowRows &win, int lane,
+                                                     typename QueuedRow<RB>::T *qx, int32_t *qrow, Keep keep, Body body) {
+    using Q = QueuedRow<RB>;
+    constexpr int R = 16 / RB;
+    const int64_t wb = win.wb, we = win.we, c0 = wb / R, c1 = (we + R - 1) / R;
+    uint4 qa[GROUP];
+    for (int64_t cg = c0; cg < c1; cg += 64 * GROUP) {   // wave-uniform
+#pragma unroll
+        for (int u = 0; u < GROUP; ++u) {
+            const int64_t c = cg + 64 * u + lane;
+            qa[u] = c < c1 ? load_row_word<RB>(rows, n_rows, c) : make_uint4(0, 0, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < GROUP; ++u) {
+            const int64_t cb = cg + 64 * u;
+            if (cb >= c1) break;   // wave-uniform
+            const int64_t c = cb + lane;
+            typename RowMask<RB>::T t[R];
+            uint32_t vm = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int64_t ri = c * R + r;
+                bool cnt, sg;
+                row_in_word<RB>(qa[u], r, t[r], cnt, sg);
+                if (c < c1 && ri >= wb && ri < we && sg && keep(t[r])) vm |= 1u << r;
+            }
+            const uint32_t ls = (uint32_t)__popc(vm);
+            const uint32_t incl = wave_incl_scan_s(ls);
+            uint32_t j = incl - ls;   // j + ls <= incl of lane 63 <= 64 * R
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if ((vm >> r) & 1u) {
+                    qx[j] = Q::put(t[r]);
+                    qrow[j] = (int32_t)(c * R + r);
+                    ++j;
+                }
+            const int nq = __builtin_amdgcn_readlane((int)incl, 63);
+            if (nq == 0) continue;
+            wave_sync();
+            body(nq);
+            wave_sync();   // the next trip's queue
+        }
     }
 }
 

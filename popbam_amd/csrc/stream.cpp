@@ -176,9 +176,9 @@ int grow(pbg_ctx *c, pbg::DevBuf &b, size_t bytes) {
     return PBG_OK;
 }
 
-// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs) is computed and copied to the host
-// a block of windows at a time, so that its device buffer and its host copy stay at kStage bytes each
-// however many windows and populations there are.
+// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin) is computed and copied
+// to the host a block of windows at a time, so that its device buffer and its host copy stay at
+// kStage bytes each however many windows and populations there are.
 constexpr size_t kStage = 64u << 20;
 struct D2H {
     void *dst;
@@ -333,7 +333,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
     switch (cmd->cmd) {
         case PBG_CMD_NUCDIV: stats = PBG_S_NUCDIV; break;
         case PBG_CMD_SFS: stats = PBG_S_SFS; break;
-        case PBG_CMD_LD: stats = cmd->output == 1 ? PBG_S_OMEGA : cmd->output == 2 ? PBG_S_WALL : PBG_S_ZNS; break;
+        case PBG_CMD_LD: stats = (cmd->output & 3) == 1 ? PBG_S_OMEGA : (cmd->output & 3) == 2 ? PBG_S_WALL : PBG_S_ZNS; break;
         case PBG_CMD_DIVERGE: stats = cmd->output == 1 ? PBG_S_DIV_POP : PBG_S_DIV_IND; break;
         case PBG_CMD_HAPLO:
             stats = cmd->output == 1 ? PBG_S_HAP_EHHS : cmd->output == 2 ? PBG_S_HAP_DXY : PBG_S_HAP_K;
@@ -487,6 +487,34 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         copies = {{h_hh.data(), d_h, got * 40}, {h_hcounts.data(), d_counts, got * hS * 4}, {h_hk.data(), d_k, got * 4}};
         return pbg_window_hfs(c, d_rows, dsites, d_win + first, cnt, &hout, s);
     };
+    // ld --rmin: the Rmin kernel over the same windows (its columns follow the reference's and
+    // --decay's).  The intervals need a stride, so a block is run twice: once for the counts alone,
+    // then, when some count is not 0, again with max_cuts = the block's largest count.  A block is
+    // sized as if that were kRminGuess; a larger one only makes the block's intervals buffer larger.
+    const bool rmin = cmd->cmd == PBG_CMD_LD && (cmd->output & PBG_LD_RMIN);
+    constexpr size_t kRminGuess = 32;
+    WinBlocks rw = win_blocks(rmin, nw, (size_t)np * (4 + 8 * kRminGuess));
+    std::vector<int32_t> h_rn, h_rcuts;
+    size_t rS = 0;   // the block's stride: intervals per (window, population)
+    auto rmin_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t got = (size_t)cnt * np, b_n = al((size_t)rw.size * np * 4);
+        int rrc = grow(c, c->sb.rmin, b_n);
+        if (rrc) return rrc;
+        const pbg_rmin_opts ropt{cmd->min_freq, 0};
+        const pbg_rmin_out rout{(int32_t *)c->sb.rmin.d, nullptr, nullptr};
+        if ((rrc = pbg_window_rmin(c, d_rows, dsites, d_win + first, cnt, &ropt, &rout, s))) return rrc;
+        h_rn.resize(got);
+        HIPCHK(c, d2h(h_rn.data(), rout.rmin, got * 4));
+        HIPCHK(c, hipStreamSynchronize(s));
+        rS = (size_t)std::max(0, *std::max_element(h_rn.begin(), h_rn.end()));
+        h_rcuts.resize(got * rS * 2);
+        if (rS == 0) return PBG_OK;
+        if ((rrc = grow(c, c->sb.rmin_cuts, got * rS * 8))) return rrc;
+        const pbg_rmin_opts copt{cmd->min_freq, (int32_t)rS};
+        const pbg_rmin_out cuts_out{nullptr, nullptr, (int32_t *)c->sb.rmin_cuts.d};
+        copies = {{h_rcuts.data(), cuts_out.cuts, got * rS * 8}};
+        return pbg_window_rmin(c, d_rows, dsites, d_win + first, cnt, &copt, &cuts_out, s);
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
@@ -512,6 +540,14 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             wh.hfs_counts = slice(h_hcounts, (size_t)(i - hw.w0) * np * hS, (size_t)np * hS);
             wh.hfs_k = slice(h_hk, (size_t)(i - hw.w0) * np, np);
             wh.hfs_stride = (int)hS;
+        }
+        if (rmin) {
+            if (i >= rw.w1 && (rc = next_block(c, s, rw, i, nw, rmin_call))) return rc;
+            wh.rmin_n = slice(h_rn, (size_t)(i - rw.w0) * np, np);
+            wh.rmin_cuts = slice(h_rcuts, (size_t)(i - rw.w0) * np * rS * 2, (size_t)np * rS * 2);
+            for (int32_t &x : wh.rmin_cuts)
+                if (x >= 0) x += (int32_t)dpos0;   // row -> contig position
+            wh.rmin_stride = (int)rS;
         }
         wh.beg = win[i].first;
         wh.end = win[i].second;
@@ -559,7 +595,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs})
+    for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs, &b.rmin, &b.rmin_cuts})
         if (x->d) (void)hipFree(x->d);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

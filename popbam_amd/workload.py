@@ -294,6 +294,41 @@ class Hfs:
         return cls(hp.ctx, hp.n_win, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
+class Rmin:
+    """pbg_window_rmin: Hudson and Kaplan's Rm and its intervals per window and population.  Owns the
+    three device arrays -- rmin[n_win, n_pops] and n_var[n_win, n_pops] (int32) and, with max_cuts > 0,
+    cuts[n_win, n_pops, max_cuts, 2] (int32: the chosen intervals' (left row, right row), then
+    (-1, -1)) -- and runs on a HotPath's rows and windows, or on any rows tensor with a window list."""
+
+    NAMES = ("rmin", "n_var", "cuts")
+
+    def __init__(self, ctx: _lib.Context, n_win: int, min_freq: int = 1, max_cuts: int = 0, device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        np_ = ctx.params.n_pops
+        self.opts = _lib.PbgRminOpts(min_freq, max_cuts)
+        self.rmin = torch.zeros((n_win, np_), dtype=torch.int32, device=device)
+        self.n_var = torch.zeros((n_win, np_), dtype=torch.int32, device=device)
+        self.cuts = torch.zeros((n_win, np_, max(max_cuts, 0), 2), dtype=torch.int32, device=device)
+        self.out = _lib.PbgRminOut(_ptr(self.rmin), _ptr(self.n_var), _ptr(self.cuts) if max_cuts > 0 else None)
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_rmin(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                            C.byref(self.opts), C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_rmin")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", min_freq: int = 1, max_cuts: int = 0, stream=None) -> "Rmin":
+        """Rm of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, min_freq, max_cuts, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 

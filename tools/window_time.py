@@ -1,5 +1,5 @@
 """The window passes on one resident batch, for one or more built checkouts:
-`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs] [--tree DIR]... [--sites 50000000]
+`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin] [--tree DIR]... [--sites 50000000]
 [--samples 12] [--pops 2] [--window 10000] [--depth 10] [--reps 25] [--seed 0xC0FFEE02] [--out FILE]`.
 
 The BASELINE configs[2] shape by default: 50 Msites x 12 samples x 2 populations, 10 kb reference
@@ -13,7 +13,9 @@ windows:
   dstat  pbg_window_dstat over all triples (i, j, k), i < j, k neither: all four outputs, and
          dstat_sums without the last stage's divisions.  Needs --pops 3 or more; skipped below that.
   hfs    pbg_window_hfs: all five outputs, and hfs_pop with k, sums and h alone
-A tree without one of the calls cannot run that pass.
+  rmin   pbg_window_rmin with rmin and n_var alone, and rmin_cuts with max_cuts = 64 and all three
+A tree without one of the calls cannot run that pass; rmin alone is skipped there (and named in
+`skipped`), since its yardstick is the decay_1x1 of the tree before it.
 
 Every --tree (default: this checkout) is measured in a fresh child process that imports that tree's
 popbam_amd package and library; this process never touches the GPU.  Two or more trees are measured
@@ -32,7 +34,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs")
+PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin")
 SHAPE = ("samples", "pops", "sites", "window", "depth", "reps", "seed")
 
 
@@ -77,6 +79,11 @@ def child(a, passes):
         hs = workload.Hfs(ctx, hp.n_win)
         hs.out.counts = hs.out.cls = None
         runs["hfs_pop"] = on_rows(hs)
+    if "rmin" in passes and not hasattr(workload, "Rmin"):
+        skipped.append("rmin")   # a tree from before the call: its decay_1x1 is the yardstick
+    elif "rmin" in passes:
+        runs["rmin"] = on_rows(workload.Rmin(ctx, hp.n_win))
+        runs["rmin_cuts"] = on_rows(workload.Rmin(ctx, hp.n_win, 1, 64))
     for f in runs.values():   # warm: plans, workspace, tables, code objects
         f()
         f()
