@@ -100,6 +100,40 @@ int check_outidx(pbg_ctx *c, const char *what, int32_t outidx, int32_t *flip_idx
     *flip_idx = outidx;
     return PBG_OK;
 }
+
+// a device window list, copied to the host for the caller to validate (this synchronises: the
+// callers cache what they validated)
+int fetch_windows(pbg_ctx *c, const pbg_window *wins, uint32_t n_win, hipStream_t stream, std::vector<pbg_window> &hw) {
+    hw.resize(n_win);
+    HIPCHK(c, hipMemcpyAsync(hw.data(), wins, n_win * sizeof(pbg_window), hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    return PBG_OK;
+}
+// The statistics workspace of pbg_window_stats and pbg_window_ld_decay: a pool the windows take
+// slices of on the device, scratch within a call (calls on one stream run in order).  `worst` is the
+// call's worst case in u64 words; the pool only ever grows, so either call's cached plans stay valid.
+constexpr uint64_t kPoolMax = 512ull << 20;   // words (4 GiB)
+int size_pool(pbg_ctx *c, uint64_t worst) {
+    return pbg::grow(c, c->ws, std::max<uint64_t>(1024, std::min(worst, kPoolMax)) * 8);
+}
+
+// pbg_kernel_time / pbg_call_time: the summed time of the event pairs used since timing was set
+int event_time(pbg_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> pbg_ctx::*pairs, double *ms_total,
+               uint32_t *launches) {
+    if (!c || !ms_total || !launches) return fail(c, PBG_E_ARG, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto &ev = c->*pairs;
+    double tot = 0.0;
+    for (size_t i = 0; i < c->ev_used; ++i) {
+        HIPCHK(c, hipEventSynchronize(ev[i].second));
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[i].first, ev[i].second));
+        tot += ms;
+    }
+    *ms_total = tot;
+    *launches = (uint32_t)c->ev_used;
+    return PBG_OK;
+}
 }  // namespace
 
 namespace pbg {
@@ -349,12 +383,13 @@ void pbg_destroy(pbg_ctx *c) {
     (void)hipSetDevice(c->device);
     pbg::stream_bufs_free(c);
     for (void *p : {(void *)c->d_fk, (void *)c->d_beta, (void *)c->d_lhet, (void *)c->d_sfs, (void *)c->d_r2,
-                    (void *)c->d_fbeta, (void *)c->d_lb, (void *)c->d_oe, c->d_scantab, (void *)c->d_err, (void *)c->d_ws, (void *)c->d_wsoff, (void *)c->d_zns,
+                    (void *)c->d_fbeta, (void *)c->d_lb, (void *)c->d_oe, c->d_scantab, (void *)c->d_err,
                     (void *)c->deep.sites, (void *)c->deep.tasks, (void *)c->deep.info, (void *)c->deep.count,
                     (void *)c->deep.blk_cnt, (void *)c->deep.raw, (void *)c->deep.pend,
-                    (void *)c->d_segcnt, (void *)c->d_synth, (void *)c->d_decay_used, (void *)c->jsfs.d_pairs,
-                    (void *)c->jsfs.d_groups})
+                    (void *)c->d_decay_used, (void *)c->jsfs.d_pairs, (void *)c->jsfs.d_groups})
         if (p) (void)hipFree(p);
+    for (pbg::DevBuf *b : {&c->ws, &c->wsoff, &c->zns, &c->segcnt, &c->synth})
+        if (b->d) (void)hipFree(b->d);
     for (auto &t : c->tmpl) (void)hipFree(t.second);
     for (auto &l : c->dstat_lists)
         if (l.d) (void)hipFree(l.d);
@@ -520,33 +555,11 @@ int pbg_set_kernel_timing(pbg_ctx *c, int on) {
 }
 
 int pbg_kernel_time(pbg_ctx *c, double *ms_total, uint32_t *launches) {
-    if (!c || !ms_total || !launches) return fail(c, PBG_E_ARG, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    double tot = 0.0;
-    for (size_t i = 0; i < c->ev_used; ++i) {
-        HIPCHK(c, hipEventSynchronize(c->ev[i].second));
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->ev[i].first, c->ev[i].second));
-        tot += ms;
-    }
-    *ms_total = tot;
-    *launches = (uint32_t)c->ev_used;
-    return PBG_OK;
+    return event_time(c, &pbg_ctx::ev, ms_total, launches);
 }
 
 int pbg_call_time(pbg_ctx *c, double *ms_total, uint32_t *launches) {
-    if (!c || !ms_total || !launches) return fail(c, PBG_E_ARG, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    double tot = 0.0;
-    for (size_t i = 0; i < c->ev_used; ++i) {
-        HIPCHK(c, hipEventSynchronize(c->evc[i].second));
-        float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->evc[i].first, c->evc[i].second));
-        tot += ms;
-    }
-    *ms_total = tot;
-    *launches = (uint32_t)c->ev_used;
-    return PBG_OK;
+    return event_time(c, &pbg_ctx::evc, ms_total, launches);
 }
 
 int pbg_window_stats(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
@@ -588,10 +601,8 @@ int pbg_window_stats(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
             segcap = pl.segcap;
         }
     if (!known) {
-        std::vector<pbg_window> hw(n_win);
-        HIPCHK(c, hipMemcpyAsync(hw.data(), wins, n_win * sizeof(pbg_window), hipMemcpyDeviceToHost,
-                                 (hipStream_t)stream));
-        HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+        std::vector<pbg_window> hw;
+        if (int rc = fetch_windows(c, wins, n_win, (hipStream_t)stream, hw)) return rc;
         uint64_t worst = 0, maxlen = 0;
         for (uint32_t i = 0; i < n_win; ++i) {
             if (hw[i].beg < 0 || hw[i].end < hw[i].beg || (uint32_t)hw[i].end > n_rows)
@@ -608,28 +619,11 @@ int pbg_window_stats(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
             if (ld_ws || len > (uint64_t)segcap) worst += mw * len + (uint64_t)n * (len / 64 + 1) + (ld_ws ? mw * np * len : 0);
             if (o->stats & PBG_S_ZNS) worst += mw * np * len;
         }
-        constexpr uint64_t kPoolMax = 512ull << 20;   // words (4 GiB)
-        const uint64_t want = std::max<uint64_t>(1024, std::min(worst, kPoolMax));
-        if (want * 8 > c->ws_cap) {
-            if (c->d_ws) HIPCHK(c, hipFree(c->d_ws));
-            c->d_ws = nullptr;
-            HIPCHK(c, hipMalloc(&c->d_ws, want * 8));
-            c->ws_cap = want * 8;
-        }
-        if ((size_t)n_win * 16 + (size_t)n_win * np * 8 + 8 > c->wsoff_cap) {   // win_off | zoff | pool_used
-            if (c->d_wsoff) HIPCHK(c, hipFree(c->d_wsoff));
-            c->d_wsoff = nullptr;
-            c->wsoff_cap = (size_t)n_win * 16 + (size_t)n_win * np * 8 + 8;
-            HIPCHK(c, hipMalloc(&c->d_wsoff, c->wsoff_cap));
-        }
+        if (int rc = size_pool(c, worst)) return rc;
+        // win_off | zoff | pool_used
+        if (int rc = pbg::grow(c, c->wsoff, (size_t)n_win * 16 + (size_t)n_win * np * 8 + 8)) return rc;
         // seg_count [n_win] | var_count [n_win*np] | ld_ns [n_win*np]
-        const size_t segcnt_bytes = (size_t)n_win * (1 + 2 * (size_t)np) * 4;
-        if (segcnt_bytes > c->segcnt_cap) {
-            if (c->d_segcnt) HIPCHK(c, hipFree(c->d_segcnt));
-            c->d_segcnt = nullptr;
-            HIPCHK(c, hipMalloc((void **)&c->d_segcnt, segcnt_bytes));
-            c->segcnt_cap = segcnt_bytes;
-        }
+        if (int rc = pbg::grow(c, c->segcnt, (size_t)n_win * (1 + 2 * (size_t)np) * 4)) return rc;
         // ZnS lists at fixed places (no pool allocation in the kernel) when windows are of
         // (nearly) one length: n_win * npops * maxlen words, at most twice the exact need
         if (o->stats & PBG_S_ZNS) {
@@ -638,29 +632,24 @@ int pbg_window_stats(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
             const uint64_t zs = mw * np * std::max<uint64_t>(maxlen, 1);
             if ((uint64_t)n_win * zs <= std::max<uint64_t>(2 * need, 1 << 20) && (uint64_t)n_win * zs <= kPoolMax) {
                 zstride = zs;
-                if ((uint64_t)n_win * zs * 8 > c->zns_cap) {
-                    if (c->d_zns) HIPCHK(c, hipFree(c->d_zns));
-                    c->d_zns = nullptr;
-                    HIPCHK(c, hipMalloc((void **)&c->d_zns, (size_t)n_win * zs * 8));
-                    c->zns_cap = (size_t)n_win * zs * 8;
-                }
+                if (int rc = pbg::grow(c, c->zns, (size_t)n_win * zs * 8)) return rc;
             }
         }
         if (c->plans.size() >= 16) c->plans.erase(c->plans.begin());
         c->plans.push_back({wins, n_win, n_rows, o->stats, zstride, segcap});
     }
-    A.pool = c->d_ws;
-    A.pool_cap = c->ws_cap / 8;
-    A.win_off = c->d_wsoff;
-    A.zoff = c->d_wsoff + 2 * (size_t)n_win;
-    A.pool_used = reinterpret_cast<unsigned long long *>(c->d_wsoff + 2 * (size_t)n_win + (size_t)n_win * np);
+    A.pool = (uint64_t *)c->ws.d;
+    A.pool_cap = c->ws.cap / 8;
+    A.win_off = (uint64_t *)c->wsoff.d;
+    A.zoff = A.win_off + 2 * (size_t)n_win;
+    A.pool_used = reinterpret_cast<unsigned long long *>(A.zoff + (size_t)n_win * np);
     A.err = c->d_err;
     HIPCHK(c, hipMemsetAsync(A.pool_used, 0, 8, (hipStream_t)stream));
-    A.zlist = c->d_zns;
+    A.zlist = (uint64_t *)c->zns.d;
     A.zstride = zstride;
-    A.seg_count = c->d_segcnt;
-    A.var_count = c->d_segcnt + n_win;
-    A.ld_ns = c->d_segcnt + n_win + (size_t)n_win * np;
+    A.seg_count = (int32_t *)c->segcnt.d;
+    A.var_count = A.seg_count + n_win;
+    A.ld_ns = A.var_count + (size_t)n_win * np;
     A.lds = pbg::stats_lds_layout(n, np, c->dp.sfs_stride, o->stats, 0, (int)mw, segcap);
     if (A.lds.bytes > 64 * 1024) return fail(c, PBG_E_ARG, "statistics need more LDS than a workgroup has");
     HIPCHK(c, pbg::launch_window_stats(c->row_bytes, c->dp, c->dt, rows, n_rows, n_win, A, (hipStream_t)stream, c->n_cu));
@@ -689,17 +678,15 @@ int pbg_window_ld_decay(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg
     A.n_bins = o->n_bins;
     A.min_freq = o->min_freq;
     const size_t lds = pbg::decay_lds_bytes(c->row_bytes, c->dp, A);
-    // The workspace is pbg_window_stats's pool: it only ever grows, so that call's cached plans stay
-    // valid; the pool is scratch within a call, and calls on one stream run in order.  Sized from the
-    // window list (every window longer than the LDS list capacity, all rows variable); validated
-    // lists are cached per device pointer like the statistics plans.
+    // The workspace is the pool pbg_window_stats uses (size_pool), sized from the window list (every
+    // window longer than the LDS list capacity, all rows variable); validated lists are cached per
+    // device pointer like the statistics plans.
     bool known = false;
     for (const auto &pl : c->decay_plans)
         if (pl.wins == (const void *)wins && pl.n_win == n_win && pl.n_rows == n_rows) known = true;
     if (!known) {
-        std::vector<pbg_window> hw(n_win);
-        HIPCHK(c, hipMemcpyAsync(hw.data(), wins, n_win * sizeof(pbg_window), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HIPCHK(c, hipStreamSynchronize((hipStream_t)stream));
+        std::vector<pbg_window> hw;
+        if (int rc = fetch_windows(c, wins, n_win, (hipStream_t)stream, hw)) return rc;
         const uint64_t mw = c->row_bytes == 16 ? 2 : 1;
         uint64_t worst = 0;
         for (uint32_t i = 0; i < n_win; ++i) {
@@ -708,21 +695,13 @@ int pbg_window_ld_decay(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg
             const uint64_t len = hw[i].end > hw[i].beg ? (uint64_t)(hw[i].end - hw[i].beg) : 0;
             if (len > (uint64_t)pbg::kDecayCap) worst += (uint64_t)np * (A.compact ? len : mw * len + (len + 1) / 2);
         }
-        constexpr uint64_t kPoolMax = 512ull << 20;   // words (4 GiB), as pbg_window_stats
-        const uint64_t want = std::max<uint64_t>(1024, std::min(worst, kPoolMax));
-        if (want * 8 > c->ws_cap) {
-            if (c->d_ws) HIPCHK(c, hipFree(c->d_ws));
-            c->d_ws = nullptr;
-            c->ws_cap = 0;
-            HIPCHK(c, hipMalloc(&c->d_ws, want * 8));
-            c->ws_cap = want * 8;
-        }
+        if (int rc = size_pool(c, worst)) return rc;
         if (c->decay_plans.size() >= 16) c->decay_plans.erase(c->decay_plans.begin());
         c->decay_plans.push_back({wins, n_win, n_rows});
     }
     if (!c->d_decay_used) HIPCHK(c, hipMalloc((void **)&c->d_decay_used, 8));
-    A.pool = c->d_ws;
-    A.pool_cap = c->ws_cap / 8;
+    A.pool = (uint64_t *)c->ws.d;
+    A.pool_cap = c->ws.cap / 8;
     A.pool_used = c->d_decay_used;
     A.err = c->d_err;
     A.pairs = out->pairs;
@@ -935,15 +914,9 @@ int pbg_synth_pileup(pbg_ctx *c, const pbg_synth_spec *sp, uint8_t *ref, void *k
         c->tmpl.emplace_back(sp->seed, t);   // cached only once built
         tmpl = t;
     }
-    const size_t need = pbg::synth_scratch_words(sp->n_sites) * 8;
-    if (need > c->synth_cap) {
-        if (c->d_synth) HIPCHK(c, hipFree(c->d_synth));
-        c->d_synth = nullptr;
-        HIPCHK(c, hipMalloc((void **)&c->d_synth, need));
-        c->synth_cap = need;
-    }
+    if (int rc = pbg::grow(c, c->synth, pbg::synth_scratch_words(sp->n_sites) * 8)) return rc;
     HIPCHK(c, pbg::launch_synth(c->dp, sp->seed, sp->contig, sp->mean_depth, sp->pos0, sp->n_sites, ref, k, rmsq,
-                                block_off, keys, keys_cap, c->d_synth, tmpl, c->d_err, s));
+                                block_off, keys, keys_cap, (uint64_t *)c->synth.d, tmpl, c->d_err, s));
     if (n_keys) {
         const uint32_t nblk = (sp->n_sites + pbg::kSiteBlock - 1) / pbg::kSiteBlock;
         HIPCHK(c, hipMemcpyAsync(n_keys, block_off + nblk, sizeof(uint64_t), hipMemcpyDeviceToHost, s));

@@ -37,7 +37,7 @@ struct WinList {                         // a device window list, kept by conten
     uint32_t dsites, n_win;
     pbg_window *d = nullptr;
 };
-struct DevBuf {                          // a device buffer that only grows (stream.cpp: grow)
+struct DevBuf {                          // a device buffer that only grows (grow, below)
     void *d = nullptr;
     size_t cap = 0;                      // bytes; 0 whenever d is null
 };
@@ -88,13 +88,12 @@ struct pbg_ctx {
         int segcap;         // segregating rows per window kept in LDS (WinLds::segcap)
     };
     std::vector<Plan> plans;
-    uint64_t *d_ws = nullptr, *d_wsoff = nullptr, *d_zns = nullptr;
-    size_t zns_cap = 0;   // bytes of d_zns
-    size_t ws_cap = 0, wsoff_cap = 0, segcnt_cap = 0;
-    int32_t *d_segcnt = nullptr;
-    // pbg_window_ld_decay: window lists already validated (their workspace need is met by ws_cap,
+    // the statistics workspace: the pool (u64 words) | win_off, zoff, pool_used | ZnS lists at fixed
+    // places | seg_count, var_count, ld_ns
+    pbg::DevBuf ws, wsoff, zns, segcnt;
+    // pbg_window_ld_decay: window lists already validated (their workspace need is met by ws,
     // which only grows), kept apart from `plans` so neither call disturbs the other's cache; and
-    // the call's own pool counter (pbg_window_stats keeps its counter in d_wsoff)
+    // the call's own pool counter (pbg_window_stats keeps its counter in wsoff)
     struct DecayPlan {
         const void *wins;
         uint32_t n_win, n_rows;
@@ -129,8 +128,7 @@ struct pbg_ctx {
     size_t ev_used = 0;
     // pbg_synth_pileup: block-total scan scratch; read-template tables per seed (built once,
     // never rebuilt while a generator launch on another stream may read them)
-    uint64_t *d_synth = nullptr;
-    size_t synth_cap = 0;
+    pbg::DevBuf synth;
     std::vector<std::pair<uint64_t, uint16_t *>> tmpl;
     // pbg_run text kept when the caller's buffer was too small (pbg_take_text)
     std::string text;
@@ -150,3 +148,16 @@ void stream_bufs_free(pbg_ctx *c);
         if (_e != hipSuccess)                                                                      \
             return ::pbg::ctx_fail((ctx), PBG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
+
+namespace pbg {
+// at least `bytes` of device memory in b.  A buffer that is too small is freed first (hipFree waits
+// for the device, so no launch still reads it); a failed allocation leaves it empty
+inline int grow(pbg_ctx *c, DevBuf &b, size_t bytes) {
+    if (b.d && b.cap >= bytes) return PBG_OK;
+    if (b.d) PBG_HIPCHK(c, hipFree(b.d));
+    b = DevBuf{};
+    PBG_HIPCHK(c, hipMalloc(&b.d, bytes));
+    b.cap = bytes;
+    return PBG_OK;
+}
+}  // namespace pbg

@@ -1,9 +1,12 @@
-// pbg_rows.h -- device helpers shared by the kernels that read packed rows.  For all of them
-// (stats_kernel.hip, decay_kernel.hip and the three below): the sample-mask types, the packed-row
-// decoder and the wave prefix sum.  For the side-table kernels (jsfs_kernel.hip, dstat_kernel.hip,
-// hfs_kernel.hip): the window clamp, the row stream that feeds a wave's LDS queue, the per-population
-// count batches of jsfs and dstat, and the launch switch over the row width.  For rmin_kernel.hip:
-// the ordered stream of a single wave.
+// pbg_rows.h -- device helpers shared by the kernels that read packed rows: the sample-mask types,
+// the packed-row decoder, the wave prefix sum, the window clamp and the launch switch over the row
+// width.  A window's rows are walked in one of two ways, each written once here:
+//   - stream_window_rows: four waves, the words dealt among them, each wave's segregating rows in
+//     an LDS queue of its own (jsfs_kernel.hip, dstat_kernel.hip, hfs_kernel.hip, with the
+//     per-population count batches of the first two);
+//   - gather_rows_in_order: one wave, the kept rows in row order with their row indices
+//     (stats_kernel.hip, and rmin_kernel.hip through stream_rows_in_order; decay_kernel.hip keeps
+//     the same loop written out, for the reason given there).
 #pragma once
 #include <type_traits>
 
@@ -229,17 +232,25 @@ __device__ __forceinline__ void stream_window_rows(const void *rows, uint32_t n_
     }
 }
 
-// The ordered stream of one wave (rmin_kernel.hip): the rows of a window in row order, each with its
-// row index.  The stream above deals a window's words to four waves and keeps no index, so it cannot
-// hand one wave a chain in order; here a single wave takes 64 consecutive words at a time, GROUP
-// trips' loads issued together (decay_kernel.hip's gather).  keep(t) decides whether a segregating row
-// of the window is queued and may narrow its bits (it runs once per such row, in no particular
-// order); body(nq) then sees qx[0 .. nq) and qrow[0 .. nq), the kept rows' bits and absolute row
-// indices in row order, under the same rules as above.  A trip queues at most 64 * (16 / RB) rows.
-template <int RB, int GROUP, class Keep, class Body>
-__device__ __forceinline__ void stream_rows_in_order(const void *rows, uint32_t n_rows, const WindowRows &win, int lane,
-                                                     typename QueuedRow<RB>::T *qx, int32_t *qrow, Keep keep, Body body) {
-    using Q = QueuedRow<RB>;
+// ---- the ordered gather of one wave (stats_kernel.hip, rmin_kernel.hip)
+//
+// The stream above deals a window's words to four waves and keeps no row index, so it cannot hand
+// one wave a window's rows in order.  Here a single wave walks the window's 16-byte words 64 at a
+// time (a trip), the loads of GROUP trips issued together so that the dependent steps wait on one
+// memory latency per group; a lane past the window's last word decodes a zero word it never loaded,
+// and the batch's last word is loaded row by row (load_row_word).
+//   keep(t, counted, seg) -> bool  runs once for every row of the window, in no particular order,
+//                                  and may narrow the row's bits t.  It also runs, without a branch,
+//                                  for the other rows of the decoded words: those come as neither
+//                                  counted nor segregating and are never kept, so a keep that acts
+//                                  on its flags alone sees the window's rows and nothing else;
+//   put(j, t, row)                 runs for every kept row: j is its rank among the trip's kept
+//                                  rows, in row order (j < 64 * (16 / RB)), row its absolute index;
+//   trip(nq)                       runs after each trip, nq its kept rows; the trip count and nq
+//                                  are wave-uniform, so trip may use wave-level barriers.
+template <int RB, int GROUP, class Keep, class Put, class Trip>
+__device__ __forceinline__ void gather_rows_in_order(const void *rows, uint32_t n_rows, const WindowRows &win, int lane,
+                                                     Keep keep, Put put, Trip trip) {
     constexpr int R = 16 / RB;
     const int64_t wb = win.wb, we = win.we, c0 = wb / R, c1 = (we + R - 1) / R;
     uint4 qa[GROUP];
@@ -259,27 +270,42 @@ __device__ __forceinline__ void stream_rows_in_order(const void *rows, uint32_t 
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const int64_t ri = c * R + r;
+                const bool in = c < c1 && ri >= wb && ri < we;
                 bool cnt, sg;
                 row_in_word<RB>(qa[u], r, t[r], cnt, sg);
-                if (c < c1 && ri >= wb && ri < we && sg && keep(t[r])) vm |= 1u << r;
+                vm |= (keep(t[r], in && cnt, in && sg) && in) ? (1u << r) : 0u;
             }
             const uint32_t ls = (uint32_t)__popc(vm);
             const uint32_t incl = wave_incl_scan_s(ls);
             uint32_t j = incl - ls;   // j + ls <= incl of lane 63 <= 64 * R
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                if ((vm >> r) & 1u) {
-                    qx[j] = Q::put(t[r]);
-                    qrow[j] = (int32_t)(c * R + r);
-                    ++j;
-                }
-            const int nq = __builtin_amdgcn_readlane((int)incl, 63);
-            if (nq == 0) continue;
-            wave_sync();
-            body(nq);
-            wave_sync();   // the next trip's queue
+                if ((vm >> r) & 1u) put(j++, t[r], c * R + r);
+            trip((uint32_t)__builtin_amdgcn_readlane((int)incl, 63));
         }
     }
+}
+
+// The gather as a stream (rmin_kernel.hip): keep(t) decides whether a segregating row of the window
+// is queued; body(nq) runs once per trip that queued nq > 0 rows and sees qx[0 .. nq) and
+// qrow[0 .. nq), the kept rows' bits and absolute row indices in row order, under the rules of
+// stream_window_rows.  A trip queues at most 64 * (16 / RB) rows, which is the queues' size.
+template <int RB, int GROUP, class Keep, class Body>
+__device__ __forceinline__ void stream_rows_in_order(const void *rows, uint32_t n_rows, const WindowRows &win, int lane,
+                                                     typename QueuedRow<RB>::T *qx, int32_t *qrow, Keep keep, Body body) {
+    using M = typename RowMask<RB>::T;
+    gather_rows_in_order<RB, GROUP>(
+        rows, n_rows, win, lane, [&](M &t, bool, bool sg) { return sg && keep(t); },
+        [&](uint32_t j, const M &t, int64_t row) {
+            qx[j] = QueuedRow<RB>::put(t);
+            qrow[j] = (int32_t)row;
+        },
+        [&](uint32_t nq) {
+            if (nq == 0) return;
+            wave_sync();
+            body((int)nq);
+            wave_sync();   // the next trip's queue
+        });
 }
 
 // jsfs and dstat: the per-population counts of the queued rows, kCntBytes / n_pops rows (>= 16) at

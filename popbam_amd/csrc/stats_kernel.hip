@@ -110,33 +110,13 @@ __global__ __launch_bounds__(64) void window_stats_kernel(DevParams P, DevTables
     const bool ld_ws = (stats & (PBG_S_OMEGA | PBG_S_WALL)) != 0;  // window_ld_kernel reads the seg list
     for (int i = lane; i < L.r2lds; i += 64) s_r2[i] = T.r2[i];
 
-    // ---- pass over the rows: counted total, ordered compaction of the segregating rows (the
-    // first segcap into LDS)
-    constexpr int R = 16 / RB;
-    const uint4 *rw = reinterpret_cast<const uint4 *>(rows);
-    const int64_t c0 = wb / R, c1 = (we + R - 1) / R;
-    auto load_word = [&](int64_t c) -> uint4 {
-        uint4 q = make_uint4(0, 0, 0, 0);
-        if (c < c1) {
-            if ((c + 1) * R <= (int64_t)n_rows) {
-                q = rw[c];
-            } else {   // the batch's last, partial 16-byte word: no read past its rows
-                uint32_t wd[4] = {0, 0, 0, 0};
-                const unsigned char *rb = reinterpret_cast<const unsigned char *>(rows) + c * 16;
-                for (int x = 0; (int64_t)c * 16 + x < (int64_t)n_rows * RB && x < 16; x += 2)
-                    wd[x >> 2] |= (uint32_t)(*reinterpret_cast<const uint16_t *>(rb + x)) << (8 * (x & 3));
-                q = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-            }
-        }
-        return q;
-    };
-    // seg rows of word c (in window): bit mask + types; `store` gets (index, types)
-    // the window's 16-byte words in groups of kLoadAhead per lane: a group's loads are issued
-    // together, so the dependent compaction steps wait on one memory latency per group
+    // ---- pass over the rows (pbg_rows.h: gather_rows_in_order): counted total, ordered compaction
+    // of the segregating rows (the first segcap into LDS).  The words of PBG_WIN_AHEAD trips per
+    // lane are loaded together.
 #ifndef PBG_WIN_AHEAD
 #define PBG_WIN_AHEAD 4
 #endif
-    constexpr int kLoadAhead = PBG_WIN_AHEAD;
+    const WindowRows win{wb, we, we <= wb};   // the host validated the list: no clamp, no error path
     // PBG_BOUNDS: a pool store at word idx must lie in the slice [sl_lo, sl_lo + sl_len) the
     // window took (compact's second pass writes there; its first pass writes LDS)
     uint64_t sl_lo = 0, sl_len = 0;
@@ -147,39 +127,17 @@ __global__ __launch_bounds__(64) void window_stats_kernel(DevParams P, DevTables
         const bool in_pool = dst != s_seg;
         (void)in_pool;
         uint32_t S = 0;
-        uint4 qa[kLoadAhead];
-        for (int64_t cg = c0; cg < c1; cg += 64 * kLoadAhead) {
-#pragma unroll
-        for (int u = 0; u < kLoadAhead; ++u) qa[u] = load_word(cg + 64 * u + lane);
-#pragma unroll
-        for (int u = 0; u < kLoadAhead; ++u) {
-            const int64_t cb = cg + 64 * u;
-            if (cb >= c1) break;   // wave-uniform
-            const int64_t c = cb + lane;
-            const uint4 q = qa[u];
-            M t[R];
-            uint32_t segm = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int64_t i = c * R + r;
-                bool cnt, sg;
-                row_in_word<RB>(q, r, t[r], cnt, sg);
-                const bool in = c < c1 && i >= wb && i < we;
-                if (count_sites) my_counted += (in && cnt) ? 1 : 0;
-                segm |= (in && sg) ? (1u << r) : 0u;
-            }
-            const uint32_t ls = (uint32_t)__popc(segm);
-            const uint32_t incl = wave_incl_scan_s(ls);
-            uint32_t j = S + incl - ls;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if ((segm >> r) & 1u) {
-                    if (j < cap && (!in_pool || pool_ok(sl_lo + (uint64_t)j * NW))) dst[j] = t[r];
-                    ++j;
-                }
-            S += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        }
-        }
+        gather_rows_in_order<RB, PBG_WIN_AHEAD>(
+            rows, n_rows, win, lane,
+            [&](M &, bool cnt, bool sg) {
+                if (count_sites) my_counted += cnt ? 1 : 0;
+                return sg;
+            },
+            [&](uint32_t k, const M &t, int64_t) {
+                const uint32_t j = S + k;
+                if (j < cap && (!in_pool || pool_ok(sl_lo + (uint64_t)j * NW))) dst[j] = t;
+            },
+            [&](uint32_t nq) { S += nq; });
         return S;
     };
     int my_counted = 0;
@@ -1043,23 +1001,15 @@ __global__ __launch_bounds__(1024) void window_zns_kernel(DevParams P, DevTables
     }
 }
 
-template __global__ void window_stats_kernel<2>(DevParams, DevTables, const void *, uint32_t, uint32_t, StatsArgs);
-template __global__ void window_stats_kernel<4>(DevParams, DevTables, const void *, uint32_t, uint32_t, StatsArgs);
-template __global__ void window_stats_kernel<8>(DevParams, DevTables, const void *, uint32_t, uint32_t, StatsArgs);
-template __global__ void window_stats_kernel<16>(DevParams, DevTables, const void *, uint32_t, uint32_t, StatsArgs);
-
 hipError_t launch_window_stats(int rb, const DevParams &P, const DevTables &T, const void *rows, uint32_t n_rows,
                                uint32_t n_win, const StatsArgs &A, hipStream_t stream, int n_cu) {
     if (n_win == 0) return hipSuccess;
     // window_stats_kernel's XCD-aware order: 8 * ceil(n_win / 8) workgroups (the extra exit at once)
     const dim3 g(n_win >= 64 ? (n_win + 7) / 8 * 8 : n_win), b(64);
     const size_t lds = A.lds.bytes;
-    switch (rb) {
-        case 2: hipLaunchKernelGGL(window_stats_kernel<2>, g, b, lds, stream, P, T, rows, n_rows, n_win, A); break;
-        case 4: hipLaunchKernelGGL(window_stats_kernel<4>, g, b, lds, stream, P, T, rows, n_rows, n_win, A); break;
-        case 8: hipLaunchKernelGGL(window_stats_kernel<8>, g, b, lds, stream, P, T, rows, n_rows, n_win, A); break;
-        default: hipLaunchKernelGGL(window_stats_kernel<16>, g, b, lds, stream, P, T, rows, n_rows, n_win, A); break;
-    }
+    dispatch_rb(rb, [&](auto RB) {
+        hipLaunchKernelGGL(window_stats_kernel<decltype(RB)::value>, g, b, lds, stream, P, T, rows, n_rows, n_win, A);
+    });
     if (A.stats & PBG_S_ZNS) {
         int r2_total = 0, max_pop = 0;
         for (int i = 0; i < P.npops; ++i) {

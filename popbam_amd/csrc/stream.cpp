@@ -165,17 +165,6 @@ int ensure_slot(pbg_ctx *c, pbg::StreamSlot &s, uint32_t chunk, size_t keys) {
     return PBG_OK;
 }
 
-// at least `bytes` of device memory in b.  A buffer that is too small is freed first (hipFree waits
-// for the device, so no launch still reads it); a failed allocation leaves it empty
-int grow(pbg_ctx *c, pbg::DevBuf &b, size_t bytes) {
-    if (b.d && b.cap >= bytes) return PBG_OK;
-    if (b.d) HIPCHK(c, hipFree(b.d));
-    b = pbg::DevBuf{};
-    HIPCHK(c, hipMalloc(&b.d, bytes));
-    b.cap = bytes;
-    return PBG_OK;
-}
-
 // A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin) is computed and copied
 // to the host a block of windows at a time, so that its device buffer and its host copy stay at
 // kStage bytes each however many windows and populations there are.
