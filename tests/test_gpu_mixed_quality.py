@@ -9,18 +9,17 @@ reads takes a mapQ from {0, 10, 13, 20, 29, 37, 45} (the rest 60), over three de
 (mean depth 2, 8 and 15: per-sample depths ~0..30).  With min_rmsQ 25 and 45 samples pass and
 fail on rms around the threshold (at 25, ~9 % of (position, sample) cells fail it alone).
 
-Each batch goes to the GPU three ways and must equal the CPU oracle (orc_call_sites, the
-reference's call chain restated) bit for bit:
+Each batch goes to the GPU three ways (call_edges.check_call_routes, routes a to c) and must
+equal the CPU oracle (orc_call_sites, the reference's call chain restated) bit for bit:
   - pbg_call_sites on a device batch, rows only (the scan's shortcuts, queues and folds);
   - pbg_call_sites with consensus words (errmod_cal + gl2cns on every task): words and rows;
   - a streamed run of the host key batch (pbg_stream_*, 64 k-position pieces): rows, and the
     nucdiv TSV against the oracle's main_nucdiv restatement (orc_run) over the same batch.
 >= 1 M positions per sample count (12, 24, 96 samples)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import call_edges
 import harness
 
 pytestmark = pytest.mark.gpu
@@ -44,91 +43,6 @@ def mixed_batch(seed, lo, hi, n, rng):
     return {"ref": ref, "depth": np.ascontiguousarray(dep), "reads": reads}
 
 
-def _names(n):
-    keep = [b"chr1", (C.c_char_p * n)(*[f"s{i}".encode() for i in range(n)]), (C.c_char_p * 2)(b"popA", b"popB")]
-    return keep
-
-
-def _oracle_nucdiv(params, batch, L, keep):
-    lib = harness.oracle()
-    c = harness.OrcCmd()
-    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq = 4, 0, 10, 10, 1
-    c.windowed, c.win_size, c.beg, c.end = 1, 10000, 0, L
-    c.chr_name = keep[0]
-    c.sample_names = C.cast(keep[1], C.POINTER(C.c_char_p))
-    c.pop_names = C.cast(keep[2], C.POINTER(C.c_char_p))
-    ref, dep = np.ascontiguousarray(batch["ref"]), np.ascontiguousarray(batch["depth"])
-    rd = np.ascontiguousarray(batch["reads"])
-    cap = 1 << 22
-    buf = C.create_string_buffer(cap)
-    r = lib.orc_run(C.byref(harness.oracle_params_from(params)), C.byref(c), L, ref.ctypes.data, dep.ctypes.data,
-                    rd.ctypes.data, buf, cap)
-    assert r >= 0
-    return buf.value.decode()
-
-
-def _check_chunk(ctx, params, batch, n):
-    import torch
-    from popbam_amd import _lib
-    L = len(batch["ref"])
-    rb = ctx.row_bytes
-    ocb, types, _, flags = harness.oracle_call(harness.oracle_params_from(params), batch)
-    expect = harness.rows_from_oracle(types, flags, rb)
-    kb = harness.key_batch(batch, params)
-    dev = {k: torch.from_numpy(np.ascontiguousarray(kb[k]).view(np.uint8).reshape(-1)).cuda()
-           for k in ("ref", "k", "rmsq", "block_off", "keys")}
-    if dev["keys"].numel() == 0:
-        dev["keys"] = torch.zeros(16, dtype=torch.uint8, device="cuda")
-    pl = _lib.PbgPileup(L, 0, *[dev[k].data_ptr() for k in ("ref", "k", "rmsq", "block_off", "keys")])
-    rows = torch.zeros(L * rb + 16, dtype=torch.uint8, device="cuda")
-    # rows only
-    ctx.check(ctx.lib.pbg_call_sites(ctx.h, C.byref(pl), rows.data_ptr(), None, None), "pbg_call_sites")
-    ctx.sync_check()
-    got = rows[:L * rb].cpu().numpy()
-    bad = np.nonzero((got.reshape(L, rb) != expect.reshape(L, rb)).any(axis=1))[0]
-    assert bad.size == 0, f"rows-only: {bad.size} rows differ, first at {bad[0]}"
-    # consensus words
-    cb = torch.zeros(L * n, dtype=torch.int64, device="cuda")
-    rows.zero_()
-    ctx.check(ctx.lib.pbg_call_sites(ctx.h, C.byref(pl), rows.data_ptr(), cb.data_ptr(), None), "pbg_call_sites")
-    ctx.sync_check()
-    cbh = cb.cpu().numpy().view(np.uint64).reshape(L, n)
-    bad = np.nonzero((cbh != ocb).any(axis=1))[0]
-    assert bad.size == 0, f"words: {bad.size} positions differ, first {bad[0]}: gpu {cbh[bad[0]]} oracle {ocb[bad[0]]}"
-    assert np.array_equal(rows[:L * rb].cpu().numpy(), expect)
-    del dev, rows, cb
-    # streamed host batch in 64 k-position pieces
-    keep = _names(n)
-    cmd = _lib.PbgCmd()
-    cmd.cmd, cmd.output, cmd.min_sites, cmd.min_snps, cmd.min_freq = 4, 0, 10, 10, 1
-    cmd.windowed, cmd.win_size, cmd.beg, cmd.end = 1, 10000, 0, L
-    cmd.chr_name = keep[0]
-    cmd.sample_names = C.cast(keep[1], C.POINTER(C.c_char_p))
-    cmd.pop_names = C.cast(keep[2], C.POINTER(C.c_char_p))
-    k2 = kb["k"].reshape(L, n)
-    boff = kb["block_off"]
-    host_rows = np.zeros(L * rb, np.uint8)
-    with _lib.Stream(ctx, [cmd], 0, L) as st:
-        piece = 1 << 16
-        for a in range(0, L, piece):
-            b = min(L, a + piece)
-            ref = np.ascontiguousarray(kb["ref"][a:b])
-            kk = np.ascontiguousarray(k2[a:b])
-            rq = np.ascontiguousarray(kb["rmsq"].reshape(L, n)[a:b])
-            k0, k1 = int(boff[a // 64]), int(boff[(b + 63) // 64])
-            keys = np.ascontiguousarray(kb["keys"][k0:k1]) if k1 > k0 else np.zeros(8, np.uint16)
-            st.push(_lib.PbgPileup(b - a, a, ref.ctypes.data, kk.ctypes.data, rq.ctypes.data, None, keys.ctypes.data))
-        st.finish()
-        st.rows_into(host_rows.ctypes.data, host_rows.size)
-        text = st.text(0)
-    bad = np.nonzero((host_rows.reshape(L, rb) != expect.reshape(L, rb)).any(axis=1))[0]
-    assert bad.size == 0, f"stream: {bad.size} rows differ, first at {bad[0]}"
-    assert text == _oracle_nucdiv(params, batch, L, keep)
-    counted = int(((flags & 2) > 0).sum())
-    failed_rms = int((((ocb >> np.uint64(48)) & np.uint64(0xFFFF)) < np.uint64(params.min_rmsQ)).sum())
-    return counted, failed_rms
-
-
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("n,chunk,total,min_rmsq", [(12, 1 << 20, 1 << 20, 25), (12, 1 << 20, 1 << 20, 45),
                                                     (24, 1 << 19, 1 << 20, 45), (96, 1 << 17, 1 << 20, 25)])
@@ -141,7 +55,7 @@ def test_mixed_quality_calls_match_oracle(gpu_lib, n, chunk, total, min_rmsq):
     try:
         for c0 in range(0, total, chunk):
             batch = mixed_batch(0xC0FFEE09 + n, c0, c0 + chunk, n, rng)
-            a, b = _check_chunk(ctx, params, batch, n)
+            a, b = call_edges.check_call_routes(ctx, params, batch, routes="abc", piece=1 << 16, nucdiv=True)
             counted += a
             failed += b
     finally:
