@@ -388,6 +388,49 @@ typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wa
 int pbg_window_rmin(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                     uint32_t n_win, const pbg_rmin_opts *opts, const pbg_rmin_out *out, void *stream);
 
+/* The per-site nSL tract sums (Ferrer-Admetlla et al. 2014) per window and population (an extension; the
+ * reference has no counterpart).  For window [beg, end) and population i (n_i samples, mask pm_i, local
+ * indices by ascending sample id) the variable sites v_0 < ... < v_{V-1} are the window's rows with the
+ * segregating bit whose m = popcount(types & pm_i) has 1 <= m <= n_i - 1, in row order: exactly
+ * pbg_window_rmin's list at min_freq = 1 (haplo has neither -e nor -p: no frequency cut, no outgroup
+ * flip).  A site's column is x_k = types & pm_i.  A pair u < v of the population's samples agrees at k
+ * when bits u and v of x_k are equal; its class there is the shared bit, 0 = the reference allele, 1 =
+ * the other.  For a pair that agrees at k, l >= 1 is the number of consecutive sites k, k-1, ... at
+ * which it agrees and r >= 1 the same through k, k+1, ...; its tract length at k is L = l + r - 1, the
+ * number of variable sites in the maximal run of agreement that contains k, cut at the window's first
+ * and last variable site.  Element (w, i) at e = w * n_pops + i has max_sites slots k:
+ *   n_var  int32 [e]: V
+ *   row    int32 [e * max_sites + k]: v_k as an absolute row index
+ *   m      int32, same index: the derived count
+ *   sl     int64 [(e * max_sites + k) * 2 + c]: the sum of L over the pairs that agree at k with class c
+ *   cens   int32 [(e * max_sites + k) * 2 + s]: the agreeing pairs, both classes together, whose run
+ *          reaches the window's first variable site (s = 0: l = k + 1) or its last (s = 1: r = V - k)
+ * Slots k >= V hold row = -1 and zeros.  A chain with V > max_sites writes every slot as unused and still
+ * reports V; nothing partial is written, and the caller reads the stride it needs from n_var.
+ * max_sites = 0 is the count-only call.  The unstandardised nSL of a site, relative to the reference
+ * allele, is formed by the caller (a device log is not reproducible): with P0 = (n_i-m)(n_i-m-1)/2 and
+ * P1 = m(m-1)/2 it is log(((double)sl0 / (double)P0) / ((double)sl1 / (double)P1)), undefined when P0
+ * or P1 is 0 and otherwise finite, since sl_c >= P_c.
+ * beg >= end gives zeros.  A window outside [0, n_rows] is not read: it gives the empty window's outputs
+ * and the next pbg_check returns PBG_E_RANGE.  A NULL member of pbg_nsl_out is skipped, except that the
+ * backward walk reads the sites back through row: sl and cens each need row.  Asynchronous; no
+ * workspace, no plan and no list of sites (one integer per sample pair, in LDS: DESIGN 3g), so a window
+ * of any length works and the call is free to interleave with every other window call on one stream.
+ * Integers only and no order that depends on scheduling: two runs give the same bytes.  PBG_E_ARG for a
+ * null ctx, rows, wins, opts or out, max_sites < 0, a non-null row, m, sl or cens with max_sites == 0,
+ * sl or cens without row, and a context whose pop_n[i] is not the number of samples in pop_mask[i];
+ * n_win == 0 returns PBG_OK. */
+typedef struct { int32_t max_sites, _pad; } pbg_nsl_opts;
+typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int32_t *n_var;            /* [n_win * n_pops]                 */
+    int32_t *row;              /* [n_win * n_pops * max_sites]     */
+    int32_t *m;                /* [n_win * n_pops * max_sites]     */
+    int64_t *sl;               /* [n_win * n_pops * max_sites * 2] */
+    int32_t *cens;             /* [n_win * n_pops * max_sites * 2] */
+} pbg_nsl_out;
+int pbg_window_nsl(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                   uint32_t n_win, const pbg_nsl_opts *opts, const pbg_nsl_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -405,6 +448,7 @@ enum { PBG_CMD_SNP = 0, PBG_CMD_HAPLO = 1, PBG_CMD_DIVERGE = 2, PBG_CMD_TREE = 3
        PBG_CMD_NUCDIV = 4, PBG_CMD_LD = 5, PBG_CMD_SFS = 6 };   /* popbam_func_t (popbam.h:208) */
 
 enum { PBG_LD_RMIN = 4 };   /* pbg_cmd.output of PBG_CMD_LD: bit 2 */
+enum { PBG_HAPLO_NSL = 4 }; /* pbg_cmd.output of PBG_CMD_HAPLO: bit 2 */
 
 typedef struct {
     int32_t  cmd;          /* PBG_CMD_*                                                   */
@@ -426,7 +470,14 @@ typedef struct {
                               left-right in 1-based contig positions, comma-separated (NA when the
                               count is 0), after the reference's columns and --decay's; they ignore
                               min_snps).  A bit of `output` and no new field: sizeof(pbg_cmd) stays,
-                              so a program compiled against the header before it keeps running    */
+                              so a program compiled against the header before it keeps running;
+                              haplo: bits 0-1 = -o (0, 1, 2), PBG_HAPLO_NSL = --nsl, again a bit and no
+                              new field (a streamed run also runs pbg_window_nsl on the command's
+                              windows and appends, per population, "nsl[pop]:" one pos:m:value:c per
+                              variable site, comma-separated -- pos the 1-based contig position,
+                              value the unstandardised nSL as %.5f or NA, c = cens[0] + cens[1] -- or
+                              NA when there is none, after the reference's columns and hfs's; they
+                              ignore min_sites)                                                   */
     int32_t  min_sites;    /* -k                                                          */
     int32_t  min_snps;     /* ld -n                                                       */
     int32_t  min_freq;     /* ld 1 / 2 (-e)                                               */
@@ -472,7 +523,7 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
  * prints the reference's columns only, whatever the command's decay_bin says; no joint-spectrum
  * arrays and no D-statistic arrays either, so sfs output bits 1 (--joint) and 2 (--dstat) add
  * nothing here; no haplotype-spectrum arrays, so haplo's hfs adds nothing here; no Rmin arrays,
- * so ld's PBG_LD_RMIN adds nothing here.                                                          */
+ * so ld's PBG_LD_RMIN adds nothing here; no nSL arrays, so haplo's PBG_HAPLO_NSL adds nothing here. */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

@@ -402,8 +402,9 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
             }
             (void)flag;
             break;
-        case PBG_CMD_HAPLO:  // print_haplo pop_haplo.cpp:365-442
-            if (c.output == 0) {
+        case PBG_CMD_HAPLO: {  // print_haplo pop_haplo.cpp:365-442
+            const int ho = c.output & 3;   // -o; bit 2 is --nsl
+            if (ho == 0) {
                 for (int i = 0; i < np; i++) {
                     const std::string p = pn(c, i);
                     o.t("\tK[" + p + "]:\t");
@@ -411,7 +412,7 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                     o.t("\tKdiv[" + p + "]:\t");
                     if (ok) o.f(w.hap_val[i]); else o.na();
                 }
-            } else if (c.output == 1) {
+            } else if (ho == 1) {
                 for (int i = 0; i < np; i++) {
                     o.t("\tEHHS[" + pn(c, i) + "]:\t");
                     if (ok && !std::isnan(w.hap_val[i])) o.f(w.hap_val[i]); else o.na();
@@ -448,7 +449,32 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                         o.i(w.hfs_counts[(size_t)i * w.hfs_stride + k]);
                     }
                 }
+            // --nsl: per population the variable sites as pos:m:value:c -- the 1-based contig position,
+            // the derived count, the unstandardised nSL log((sl0 / P0) / (sl1 / P1)) (NA when a class
+            // has no pair) and the number of tracts the window cut short -- after the reference's
+            // columns and --hfs's (any -o); not subject to -k
+            if ((c.output & PBG_HAPLO_NSL) && (int)w.nsl_n.size() == np && (int)w.nsl_pn.size() == np &&
+                w.nsl_pos.size() == (size_t)np * w.nsl_stride && w.nsl_m.size() == w.nsl_pos.size() &&
+                w.nsl_sl.size() == 2 * w.nsl_pos.size() && w.nsl_cens.size() == 2 * w.nsl_pos.size())
+                for (int i = 0; i < np; i++) {
+                    o.t("\tnsl[" + pn(c, i) + "]:\t");
+                    if (w.nsl_n[i] <= 0) o.t("NA");
+                    for (int k = 0; k < w.nsl_n[i] && k < w.nsl_stride; k++) {
+                        const size_t at = (size_t)i * w.nsl_stride + k;
+                        const long long m = w.nsl_m[at], z = w.nsl_pn[i] - m, p0 = z * (z - 1) / 2, p1 = m * (m - 1) / 2;
+                        if (k) o.t(",");
+                        o.i(w.nsl_pos[at] + 1);
+                        o.t(":");
+                        o.i(m);
+                        o.t(":");
+                        if (p0 == 0 || p1 == 0) o.t("NA");
+                        else o.f(std::log(((double)w.nsl_sl[2 * at] / (double)p0) / ((double)w.nsl_sl[2 * at + 1] / (double)p1)));
+                        o.t(":");
+                        o.i((long long)w.nsl_cens[2 * at] + w.nsl_cens[2 * at + 1]);
+                    }
+                }
             break;
+        }
         case PBG_CMD_TREE:
             format_nj(o, c, n, w);
             break;

@@ -402,6 +402,23 @@ struct RminArgs {
     int32_t *cuts;             // [n_win * npops * max_cuts * 2] or null
 };
 
+// window_nsl_kernel (pbg_window_nsl): the per-site nSL tract sums per (window, population).  One wave
+// per chain; a chain's row queue, one int32 per sample pair and the pair table live in LDS, so there is
+// no workspace.  The launcher sizes the per-wave LDS from the largest population and picks the waves
+// per workgroup (4, 2 or 1) that keep a launch within 64 KiB.
+struct NslArgs {
+    const pbg_window *wins;
+    int *err;
+    int32_t max_sites;
+    int32_t pairs_max, waves;  // set by the launcher: n (n - 1) / 2 of the largest population; chains per workgroup
+    uint32_t wave_bytes;       // set by the launcher: LDS per wave
+    int32_t *n_var;            // [n_win * npops] or null
+    int32_t *row;              // [n_win * npops * max_sites] or null
+    int32_t *m;                // [n_win * npops * max_sites] or null
+    int64_t *sl;               // [n_win * npops * max_sites * 2] or null
+    int32_t *cens;             // [n_win * npops * max_sites * 2] or null
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -550,5 +567,9 @@ hipError_t launch_window_hfs(int row_bytes, const DevParams &P, const void *rows
 // rmin_kernel.hip (static LDS only)
 hipError_t launch_window_rmin(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                               const RminArgs &A, hipStream_t stream);
+// nsl_kernel.hip (dynamic LDS: waves * nsl_wave_bytes(row_bytes, pairs of the largest population))
+size_t nsl_wave_bytes(int row_bytes, int pairs_max);
+hipError_t launch_window_nsl(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                             NslArgs A, hipStream_t stream);
 
 }  // namespace pbg

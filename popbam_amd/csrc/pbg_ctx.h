@@ -52,6 +52,7 @@ struct StreamBufs {
     DevBuf dstat;                        // sfs --dstat: sums | d | fd | fdm of one block of windows
     DevBuf hfs;                          // haplo --hfs: h | counts | k of one block of windows
     DevBuf rmin, rmin_cuts;              // ld --rmin: the counts and the intervals of one block of windows
+    DevBuf nsl, nsl_sites;               // haplo --nsl: n_var, and row | m | cens | sl of one block of windows
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };

@@ -56,6 +56,13 @@ struct WindowHost {
     // (pbg_window_rmin); empty when the caller has none (pbg_format)
     std::vector<int32_t> rmin_n, rmin_cuts;
     int rmin_stride = 0;
+    // haplo --nsl (PBG_HAPLO_NSL in pbg_cmd.output): population p has nsl_n[p] variable sites; site k at
+    // s = p * nsl_stride + k: nsl_pos[s] its contig position, 0-based, nsl_m[s] the derived count,
+    // nsl_sl[2 * s + c] and nsl_cens[2 * s + side] the sums of pbg_window_nsl; nsl_pn[p] the
+    // population's size; empty when the caller has none (pbg_format)
+    std::vector<int32_t> nsl_n, nsl_pos, nsl_m, nsl_cens, nsl_pn;
+    std::vector<int64_t> nsl_sl;
+    int nsl_stride = 0;
 };
 
 // sfs --dstat's triples of n_pops populations: all (i, j, k) with i < j and k neither, in

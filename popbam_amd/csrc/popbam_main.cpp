@@ -101,6 +101,7 @@ struct Options {
     int decay_bin = 0, decay_bins = 0;                                    // ld --decay=BIN,NBINS (0: off)
     int hfs = 0;                                                          // haplo --hfs (0: off)
     int rmin = 0;                                                         // ld --rmin (0: off)
+    int nsl = 0;                                                          // haplo --nsl (0: off)
     unsigned int win_size = 0;
     long double het_prior = 0.0001L;                                      // -z: parsed, unused
 };
@@ -290,6 +291,8 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
         o.output |= 4;   // extension: D, f_d, f_dM and their sums of every population triple after those
     if (cmd == "haplo" && std::find(argv.begin(), argv.end(), std::string("--hfs")) != argv.end())
         o.hfs = 1;   // extension: H1, H12, H123, H2H1, Hd and the class sizes of every population (any -o)
+    if (cmd == "haplo" && std::find(argv.begin(), argv.end(), std::string("--nsl")) != argv.end())
+        o.nsl = 1;   // extension: the per-site nSL of every population (any -o, also with --hfs)
     if (cmd == "ld" && std::find(argv.begin(), argv.end(), std::string("--rmin")) != argv.end())
         o.rmin = 1;   // extension: Hudson and Kaplan's Rm and its intervals of every population (any -o)
     if (cmd == "ld" && tk.present('e')) o.min_freq = 2;
@@ -756,7 +759,7 @@ std::string run(const std::string &cmd, const std::vector<std::string> &argv, in
         hi = std::max(hi, lo);
         pbg_cmd c{};
         c.cmd = cmd_id(cmd);
-        c.output = o.output | (cmd == "ld" && o.rmin ? PBG_LD_RMIN : 0);
+        c.output = o.output | (cmd == "ld" && o.rmin ? PBG_LD_RMIN : 0) | (cmd == "haplo" && o.nsl ? PBG_HAPLO_NSL : 0);
         c.min_sites = o.min_sites;
         c.min_snps = o.min_snps;
         c.min_freq = o.min_freq;

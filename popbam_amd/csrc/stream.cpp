@@ -165,7 +165,7 @@ int ensure_slot(pbg_ctx *c, pbg::StreamSlot &s, uint32_t chunk, size_t keys) {
     return PBG_OK;
 }
 
-// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin) is computed and copied
+// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin, haplo --nsl) is computed and copied
 // to the host a block of windows at a time, so that its device buffer and its host copy stay at
 // kStage bytes each however many windows and populations there are.
 constexpr size_t kStage = 64u << 20;
@@ -325,7 +325,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         case PBG_CMD_LD: stats = (cmd->output & 3) == 1 ? PBG_S_OMEGA : (cmd->output & 3) == 2 ? PBG_S_WALL : PBG_S_ZNS; break;
         case PBG_CMD_DIVERGE: stats = cmd->output == 1 ? PBG_S_DIV_POP : PBG_S_DIV_IND; break;
         case PBG_CMD_HAPLO:
-            stats = cmd->output == 1 ? PBG_S_HAP_EHHS : cmd->output == 2 ? PBG_S_HAP_DXY : PBG_S_HAP_K;
+            stats = (cmd->output & 3) == 1 ? PBG_S_HAP_EHHS : (cmd->output & 3) == 2 ? PBG_S_HAP_DXY : PBG_S_HAP_K;
             break;
         case PBG_CMD_TREE:
             // join_tree's last cycle needs three clusters (ntaxa = n + 1 >= 3)
@@ -504,6 +504,43 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         copies = {{h_rcuts.data(), cuts_out.cuts, got * rS * 8}};
         return pbg_window_rmin(c, d_rows, dsites, d_win + first, cnt, &copt, &cuts_out, s);
     };
+    // haplo --nsl: the nSL kernel over the same windows (its columns follow the reference's and
+    // --hfs's).  The per-site arrays need a stride, so a block is run twice as for --rmin: once for
+    // the counts alone, then, when some count is not 0, again with max_sites = the block's largest
+    // count.  A block is sized as if that were kNslGuess; a larger one only makes the block's
+    // per-site buffer larger.
+    const bool nsl = cmd->cmd == PBG_CMD_HAPLO && (cmd->output & PBG_HAPLO_NSL);
+    constexpr size_t kNslGuess = 256, kNslSite = 4 + 4 + 8 + 16;   // row, m, cens, sl: bytes per slot
+    WinBlocks nb = win_blocks(nsl, nw, (size_t)np * (4 + kNslSite * kNslGuess));
+    std::vector<int32_t> h_nn, h_nrow, h_nm, h_ncens;
+    std::vector<int64_t> h_nsl;
+    size_t nS = 0;   // the block's stride: slots per (window, population)
+    auto nsl_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t got = (size_t)cnt * np;
+        int nrc = grow(c, c->sb.nsl, al((size_t)nb.size * np * 4));
+        if (nrc) return nrc;
+        const pbg_nsl_opts nopt{0, 0};
+        const pbg_nsl_out nout{(int32_t *)c->sb.nsl.d, nullptr, nullptr, nullptr, nullptr};
+        if ((nrc = pbg_window_nsl(c, d_rows, dsites, d_win + first, cnt, &nopt, &nout, s))) return nrc;
+        h_nn.resize(got);
+        HIPCHK(c, d2h(h_nn.data(), nout.n_var, got * 4));
+        HIPCHK(c, hipStreamSynchronize(s));
+        nS = (size_t)std::max(0, *std::max_element(h_nn.begin(), h_nn.end()));
+        const size_t slots = got * nS;
+        h_nrow.resize(slots);
+        h_nm.resize(slots);
+        h_ncens.resize(slots * 2);
+        h_nsl.resize(slots * 2);
+        if (nS == 0) return PBG_OK;
+        if ((nrc = grow(c, c->sb.nsl_sites, slots * kNslSite))) return nrc;
+        int64_t *d_sl = (int64_t *)c->sb.nsl_sites.d;   // the widest first: every part stays aligned
+        int32_t *d_cens = (int32_t *)(d_sl + slots * 2), *d_row = d_cens + slots * 2, *d_m = d_row + slots;
+        const pbg_nsl_opts sopt{(int32_t)nS, 0};
+        const pbg_nsl_out sout{nullptr, d_row, d_m, d_sl, d_cens};
+        copies = {{h_nrow.data(), d_row, slots * 4}, {h_nm.data(), d_m, slots * 4}, {h_ncens.data(), d_cens, slots * 8},
+                  {h_nsl.data(), d_sl, slots * 16}};
+        return pbg_window_nsl(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
@@ -537,6 +574,19 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             for (int32_t &x : wh.rmin_cuts)
                 if (x >= 0) x += (int32_t)dpos0;   // row -> contig position
             wh.rmin_stride = (int)rS;
+        }
+        if (nsl) {
+            if (i >= nb.w1 && (rc = next_block(c, s, nb, i, nw, nsl_call))) return rc;
+            const size_t e0 = (size_t)(i - nb.w0) * np, per = (size_t)np * nS;
+            wh.nsl_n = slice(h_nn, e0, np);
+            wh.nsl_pos = slice(h_nrow, e0 * nS, per);
+            for (int32_t &x : wh.nsl_pos)
+                if (x >= 0) x += (int32_t)dpos0;   // row -> contig position
+            wh.nsl_m = slice(h_nm, e0 * nS, per);
+            wh.nsl_cens = slice(h_ncens, e0 * nS * 2, per * 2);
+            wh.nsl_sl = slice(h_nsl, e0 * nS * 2, per * 2);
+            wh.nsl_pn.assign(c->dp.pop_n, c->dp.pop_n + np);
+            wh.nsl_stride = (int)nS;
         }
         wh.beg = win[i].first;
         wh.end = win[i].second;
@@ -584,7 +634,8 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
 void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
-    for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs, &b.rmin, &b.rmin_cuts})
+    for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs, &b.rmin, &b.rmin_cuts, &b.nsl,
+                            &b.nsl_sites})
         if (x->d) (void)hipFree(x->d);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

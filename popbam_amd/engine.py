@@ -59,6 +59,8 @@ class _Cmd:
         c.output, c.min_sites, c.min_snps, c.min_freq = o.output, o.min_sites, o.min_snps, o.min_freq
         if o.cmd == "ld" and o.rmin:
             c.output |= _lib.PBG_LD_RMIN
+        if o.cmd == "haplo" and o.nsl:
+            c.output |= _lib.PBG_HAPLO_NSL
         c.outidx = 0
         if o.flag & opt.BAM_OUTGROUP and o.cmd in ("sfs", "diverge", "snp"):   # nucdiv sets the flag, never reads -p
             idx = [i for i, s in enumerate(sm.samples) if s == o.outgroup]

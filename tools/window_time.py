@@ -1,5 +1,5 @@
 """The window passes on one resident batch, for one or more built checkouts:
-`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin] [--tree DIR]... [--sites 50000000]
+`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin,nsl] [--tree DIR]... [--sites 50000000]
 [--samples 12] [--pops 2] [--window 10000] [--depth 10] [--reps 25] [--seed 0xC0FFEE02] [--out FILE]`.
 
 The BASELINE configs[2] shape by default: 50 Msites x 12 samples x 2 populations, 10 kb reference
@@ -14,8 +14,11 @@ windows:
          dstat_sums without the last stage's divisions.  Needs --pops 3 or more; skipped below that.
   hfs    pbg_window_hfs: all five outputs, and hfs_pop with k, sums and h alone
   rmin   pbg_window_rmin with rmin and n_var alone, and rmin_cuts with max_cuts = 64 and all three
-A tree without one of the calls cannot run that pass; rmin alone is skipped there (and named in
-`skipped`), since its yardstick is the decay_1x1 of the tree before it.
+  nsl    pbg_window_nsl count-only (max_sites = 0) as nsl_nvar, and nsl, the full call with all five
+         outputs and max_sites = the largest count nsl_nvar found
+A tree without one of the calls cannot run that pass; rmin and nsl alone are skipped there (and named
+in `skipped`): rmin's yardstick is the decay_1x1 of the tree before it, nsl's is that tree's rmin, and
+with two trees the comparison sets nsl_nvar against the first tree's rmin and gives nsl's ratio to it.
 
 Every --tree (default: this checkout) is measured in a fresh child process that imports that tree's
 popbam_amd package and library; this process never touches the GPU.  Two or more trees are measured
@@ -34,7 +37,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin")
+PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin", "nsl")
 SHAPE = ("samples", "pops", "sites", "window", "depth", "reps", "seed")
 
 
@@ -84,6 +87,18 @@ def child(a, passes):
     elif "rmin" in passes:
         runs["rmin"] = on_rows(workload.Rmin(ctx, hp.n_win))
         runs["rmin_cuts"] = on_rows(workload.Rmin(ctx, hp.n_win, 1, 64))
+    extra = {}
+    if "nsl" in passes and not hasattr(workload, "Nsl"):
+        skipped.append("nsl")   # a tree from before the call: its rmin is the yardstick
+    elif "nsl" in passes:
+        cnt = workload.Nsl(ctx, hp.n_win)
+        runs["nsl_nvar"] = on_rows(cnt)
+        cnt(hp.rows, hp.wins, sites)
+        ctx.sync_check()
+        extra["nsl_max_sites"] = int(cnt.n_var.max().item())
+        extra["nsl_sites"] = int(cnt.n_var.sum().item())
+        if extra["nsl_max_sites"] > 0:
+            runs["nsl"] = on_rows(workload.Nsl(ctx, hp.n_win, extra["nsl_max_sites"]))
     for f in runs.values():   # warm: plans, workspace, tables, code objects
         f()
         f()
@@ -101,7 +116,7 @@ def child(a, passes):
     out = {"tree": "this" if a.tree[0] == REPO else "other: " + os.path.basename(a.tree[0]), "sites": sites,
            "samples": a.samples, "pops": a.pops, "window": a.window, "windows": hp.n_win, "reps": a.reps,
            "segsites": int(hp.out.t["segsites"].sum().item()), "lib": ctx.lib.pbg_build_info().decode(),
-           "skipped": skipped}
+           "skipped": skipped, **extra}
     for nm, v in ms.items():
         out[nm + "_ms_median"] = round(statistics.median(v), 4)
         out[nm + "_ms_min"] = round(min(v), 4)
@@ -120,6 +135,15 @@ def compare(first, second):
         margin = max(max(a) - min(a), 0.02 * base)
         cmp[key[:-len("_ms_median")]] = {"first_ms": round(base, 4), "second_ms": round(new, 4), "margin_ms": round(margin, 4),
                                          "ok": new <= base + margin}
+    if "rmin_ms_median" in first[0] and "nsl_nvar_ms_median" in second[0]:   # nsl against the first tree's rmin
+        a = [r["rmin_ms_median"] for r in first]
+        base = statistics.mean(a)
+        margin = max(max(a) - min(a), 0.02 * base)
+        for nm in ("nsl_nvar", "nsl"):
+            if nm + "_ms_median" in second[0]:
+                new = statistics.mean(r[nm + "_ms_median"] for r in second)
+                cmp[nm] = {"first_rmin_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
+        cmp["nsl_nvar"].update(margin_ms=round(margin, 4), ok=cmp["nsl_nvar"]["second_ms"] <= base + margin)
     return cmp
 
 
