@@ -431,6 +431,51 @@ typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wa
 int pbg_window_nsl(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                    uint32_t n_win, const pbg_nsl_opts *opts, const pbg_nsl_out *out, void *stream);
 
+/* The cross-population nSL tract sums (XP-nSL, Szpiech et al. 2021: the map-free form of XP-EHH) per
+ * window and population pair (an extension; the reference has no counterpart).  Population pairs are
+ * (i, j), i < j, in lexicographic order -- pbg_window_jsfs's order -- with pair index p = 0 .. n_pairs-1,
+ * n_pairs = n_pops (n_pops - 1) / 2; populations are disjoint (pbg_create refuses overlapping masks).
+ * For window [beg, end) and pair (i, j) the pooled sites v_0 < ... < v_{V-1} are the window's rows with
+ * the segregating bit whose pooled count m = popcount(types & (pm_i | pm_j)) has 1 <= m <= n_i + n_j - 1,
+ * in row order: the list pbg_window_nsl produces in a context whose single population is pm_i | pm_j, so
+ * it includes the sites fixed in one of the two.  Side s = 0 is population i, side s = 1 population j.  A
+ * sample pair u < v of a side agrees at k when bits u and v of types[v_k] are equal; either allele counts,
+ * there are no classes.  For a pair that agrees at k, l >= 1 and r >= 1 are its runs of agreement through
+ * k, k-1, ... and k, k+1, ... over the POOLED list, and its tract length is L = l + r - 1, cut at the
+ * window's first and last pooled site; a pair that differs at k contributes 0.  Element (w, p) at
+ * e = w * n_pairs + p has max_sites slots k:
+ *   n_var  int32 [e]: V
+ *   row    int32 [e * max_sites + k]: v_k as an absolute row index
+ *   m      int32 [(e * max_sites + k) * 2 + s]: side s's derived count; may be 0 or n_s
+ *   sl     int64, same index: the sum of L over side s's agreeing pairs
+ *   cens   int32, same index: side s's agreeing pairs with l = k + 1, plus those with r = V - k (a pair
+ *          that agrees across the whole window counts twice)
+ * Slots k >= V hold row = -1 and zeros.  A chain with V > max_sites writes every slot as unused and still
+ * reports V; nothing partial is written.  max_sites = 0 is the count-only call.  The unstandardised
+ * XP-nSL of a site is formed by the caller (a device log is not reproducible): with C_s = n_s (n_s-1) / 2
+ * it is log(((double)sl_0 / C_0) / ((double)sl_1 / C_1)), positive when population i carries the longer
+ * tracts, undefined when C_0 or C_1 is 0 or when sl_0 or sl_1 is 0 (a side of two samples that differ at
+ * the site).  beg >= end gives zeros.  A window outside [0, n_rows] is not read: it gives the empty
+ * window's outputs and the next pbg_check returns PBG_E_RANGE.  A NULL member of pbg_xpnsl_out is
+ * skipped, except that the backward walk reads the sites back through row: sl and cens each need row.
+ * Asynchronous; no workspace, no plan and no list of sites (one integer per sample pair of the two
+ * sides, in LDS: DESIGN 3h), so a window of any length works and the call is free to interleave with
+ * every other window call on one stream.  Integers only and no order that depends on scheduling: two
+ * runs give the same bytes.  PBG_E_ARG for a null ctx, rows, wins, opts or out, max_sites < 0, a
+ * non-null row, m, sl or cens with max_sites == 0, sl or cens without row, and a context whose pop_n[i]
+ * is not the number of samples in pop_mask[i]; n_win == 0 returns PBG_OK, and so does a context with one
+ * population (n_pairs = 0), which writes nothing. */
+typedef struct { int32_t max_sites, _pad; } pbg_xpnsl_opts;
+typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int32_t *n_var;            /* [n_win * n_pairs]                 */
+    int32_t *row;              /* [n_win * n_pairs * max_sites]     */
+    int32_t *m;                /* [n_win * n_pairs * max_sites * 2] */
+    int64_t *sl;               /* [n_win * n_pairs * max_sites * 2] */
+    int32_t *cens;             /* [n_win * n_pairs * max_sites * 2] */
+} pbg_xpnsl_out;
+int pbg_window_xpnsl(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                     uint32_t n_win, const pbg_xpnsl_opts *opts, const pbg_xpnsl_out *out, void *stream);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -449,6 +494,7 @@ enum { PBG_CMD_SNP = 0, PBG_CMD_HAPLO = 1, PBG_CMD_DIVERGE = 2, PBG_CMD_TREE = 3
 
 enum { PBG_LD_RMIN = 4 };   /* pbg_cmd.output of PBG_CMD_LD: bit 2 */
 enum { PBG_HAPLO_NSL = 4 }; /* pbg_cmd.output of PBG_CMD_HAPLO: bit 2 */
+enum { PBG_HAPLO_XPNSL = 8 }; /* pbg_cmd.output of PBG_CMD_HAPLO: bit 3 */
 
 typedef struct {
     int32_t  cmd;          /* PBG_CMD_*                                                   */
@@ -477,7 +523,12 @@ typedef struct {
                               variable site, comma-separated -- pos the 1-based contig position,
                               value the unstandardised nSL as %.5f or NA, c = cens[0] + cens[1] -- or
                               NA when there is none, after the reference's columns and hfs's; they
-                              ignore min_sites)                                                   */
+                              ignore min_sites); PBG_HAPLO_XPNSL = --xpnsl, a bit likewise (a streamed
+                              run also runs pbg_window_xpnsl and appends, per population pair i < j,
+                              "xpnsl[popI,popJ]:" one pos:mI:mJ:value:c per pooled site -- value the
+                              unstandardised XP-nSL as %.5f or NA, c = cens[0] + cens[1] -- or NA when
+                              there is none, after --nsl's columns; nothing with fewer than two
+                              populations; they ignore min_sites)                                 */
     int32_t  min_sites;    /* -k                                                          */
     int32_t  min_snps;     /* ld -n                                                       */
     int32_t  min_freq;     /* ld 1 / 2 (-e)                                               */
@@ -523,7 +574,8 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
  * prints the reference's columns only, whatever the command's decay_bin says; no joint-spectrum
  * arrays and no D-statistic arrays either, so sfs output bits 1 (--joint) and 2 (--dstat) add
  * nothing here; no haplotype-spectrum arrays, so haplo's hfs adds nothing here; no Rmin arrays,
- * so ld's PBG_LD_RMIN adds nothing here; no nSL arrays, so haplo's PBG_HAPLO_NSL adds nothing here. */
+ * so ld's PBG_LD_RMIN adds nothing here; no nSL arrays, so haplo's PBG_HAPLO_NSL adds nothing here;
+ * no XP-nSL arrays, so haplo's PBG_HAPLO_XPNSL adds nothing here. */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

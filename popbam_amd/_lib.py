@@ -31,11 +31,13 @@ EXPORTS = ["pbg_create", "pbg_destroy", "pbg_last_error", "pbg_row_bytes", "pbg_
            "pbg_synth_pileup", "pbg_stream_open", "pbg_stream_push", "pbg_stream_push_compact", "pbg_stream_finish", "pbg_stream_text",
            "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay",
            "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs", "pbg_window_dstat",
-           "pbg_hfs_stride", "pbg_window_hfs", "pbg_window_rmin", "pbg_window_nsl"]
+           "pbg_hfs_stride", "pbg_window_hfs", "pbg_window_rmin", "pbg_window_nsl",
+           "pbg_window_xpnsl"]
 
 PBG_DECAY_MAX_BINS = 256
 PBG_LD_RMIN = 4   # pbg_cmd.output of PBG_CMD_LD: --rmin
 PBG_HAPLO_NSL = 4   # pbg_cmd.output of PBG_CMD_HAPLO: --nsl
+PBG_HAPLO_XPNSL = 8   # pbg_cmd.output of PBG_CMD_HAPLO: --xpnsl
 PBG_DSTAT_MAX_TRIPLES = 4096
 
 
@@ -136,6 +138,14 @@ class PbgNslOut(C.Structure):
     _fields_ = [("n_var", C.c_void_p), ("row", C.c_void_p), ("m", C.c_void_p), ("sl", C.c_void_p), ("cens", C.c_void_p)]
 
 
+class PbgXpnslOpts(C.Structure):
+    _fields_ = [("max_sites", C.c_int32), ("_pad", C.c_int32)]
+
+
+class PbgXpnslOut(C.Structure):
+    _fields_ = [("n_var", C.c_void_p), ("row", C.c_void_p), ("m", C.c_void_p), ("sl", C.c_void_p), ("cens", C.c_void_p)]
+
+
 class PbgStreamProf(C.Structure):
     _fields_ = [("h2d_bytes", C.c_uint64), ("pieces", C.c_uint32), ("chunks", C.c_uint32),
                 ("pinned_chunks", C.c_uint32), ("_pad", C.c_uint32), ("ms_stage", C.c_double),
@@ -205,6 +215,8 @@ def load(torch_first: bool = True):
     lib.pbg_window_rmin.restype = C.c_int
     lib.pbg_window_nsl.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgNslOpts), P(PbgNslOut), vp]
     lib.pbg_window_nsl.restype = C.c_int
+    lib.pbg_window_xpnsl.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgXpnslOpts), P(PbgXpnslOut), vp]
+    lib.pbg_window_xpnsl.restype = C.c_int
     lib.pbg_build_info.argtypes = []
     lib.pbg_build_info.restype = C.c_char_p
     lib.pbg_check.argtypes = [vp, vp]

@@ -138,7 +138,7 @@ int event_time(pbg_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> pbg_ct
 
 namespace pbg {
 extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat, kBuildKind_hfs,
-    kBuildKind_rmin, kBuildKind_nsl;
+    kBuildKind_rmin, kBuildKind_nsl, kBuildKind_xpnsl;
 }
 
 namespace {
@@ -522,7 +522,7 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 const char *pbg_build_info(void) {
     const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay,
                                pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat, pbg::kBuildKind_hfs, pbg::kBuildKind_rmin,
-                               pbg::kBuildKind_nsl});
+                               pbg::kBuildKind_nsl, pbg::kBuildKind_xpnsl});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -901,6 +901,30 @@ int pbg_window_nsl(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wind
     A.sl = out->sl;
     A.cens = out->cens;
     HIPCHK(c, pbg::launch_window_nsl(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    return PBG_OK;
+}
+
+int pbg_window_xpnsl(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                     const pbg_xpnsl_opts *o, const pbg_xpnsl_out *out, void *stream) {
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    if (o->max_sites < 0) return fail(c, PBG_E_ARG, "xpnsl: max_sites must not be negative");
+    if ((out->row || out->m || out->sl || out->cens) && o->max_sites == 0)
+        return fail(c, PBG_E_ARG, "xpnsl: row, m, sl and cens need max_sites of at least 1");
+    if ((out->sl || out->cens) && !out->row) return fail(c, PBG_E_ARG, "xpnsl: sl and cens need row");
+    if (int rc = check_pop_sizes(c, "xpnsl")) return rc;   // the pairs come from pop_n, the samples from pop_mask
+    if (n_win == 0 || c->dp.npops < 2) return PBG_OK;      // one population has no pair: nothing is written
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    pbg::XpnslArgs A{};
+    A.wins = wins;
+    A.err = c->d_err;
+    A.max_sites = o->max_sites;
+    A.n_var = out->n_var;
+    A.row = out->row;
+    A.m = out->m;
+    A.sl = out->sl;
+    A.cens = out->cens;
+    HIPCHK(c, pbg::launch_window_xpnsl(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
     return PBG_OK;
 }
 

@@ -403,7 +403,7 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
             (void)flag;
             break;
         case PBG_CMD_HAPLO: {  // print_haplo pop_haplo.cpp:365-442
-            const int ho = c.output & 3;   // -o; bit 2 is --nsl
+            const int ho = c.output & 3;   // -o; bit 2 is --nsl, bit 3 --xpnsl
             if (ho == 0) {
                 for (int i = 0; i < np; i++) {
                     const std::string p = pn(c, i);
@@ -473,6 +473,37 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                         o.i((long long)w.nsl_cens[2 * at] + w.nsl_cens[2 * at + 1]);
                     }
                 }
+            // --xpnsl: per population pair (i < j) the pooled sites as pos:mI:mJ:value:c -- the 1-based contig
+            // position, the two derived counts, the unstandardised XP-nSL log((sl_i / C_i) / (sl_j / C_j))
+            // with C = n (n - 1) / 2 (NA when a side has no pair, or two samples that differ) and the number
+            // of tracts the window cut short, both sides together -- after --nsl's columns; not subject to -k
+            const size_t xp = (size_t)np * (np - 1) / 2;
+            if ((c.output & PBG_HAPLO_XPNSL) && xp > 0 && w.xp_n.size() == xp && (int)w.xp_pn.size() == np &&
+                w.xp_pos.size() == xp * w.xp_stride && w.xp_m.size() == 2 * w.xp_pos.size() &&
+                w.xp_sl.size() == 2 * w.xp_pos.size() && w.xp_cens.size() == 2 * w.xp_pos.size()) {
+                size_t p = 0;
+                for (int i = 0; i < np; i++)
+                    for (int j = i + 1; j < np; j++, p++) {
+                        o.t("\txpnsl[" + pn(c, i) + "," + pn(c, j) + "]:\t");
+                        if (w.xp_n[p] <= 0) o.t("NA");
+                        const long long c0 = (long long)w.xp_pn[i] * (w.xp_pn[i] - 1) / 2, c1 = (long long)w.xp_pn[j] * (w.xp_pn[j] - 1) / 2;
+                        for (int k = 0; k < w.xp_n[p] && k < w.xp_stride; k++) {
+                            const size_t at = p * w.xp_stride + k;
+                            const long long s0 = w.xp_sl[2 * at], s1 = w.xp_sl[2 * at + 1];
+                            if (k) o.t(",");
+                            o.i(w.xp_pos[at] + 1);
+                            o.t(":");
+                            o.i(w.xp_m[2 * at]);
+                            o.t(":");
+                            o.i(w.xp_m[2 * at + 1]);
+                            o.t(":");
+                            if (c0 == 0 || c1 == 0 || s0 == 0 || s1 == 0) o.t("NA");
+                            else o.f(std::log(((double)s0 / (double)c0) / ((double)s1 / (double)c1)));
+                            o.t(":");
+                            o.i((long long)w.xp_cens[2 * at] + w.xp_cens[2 * at + 1]);
+                        }
+                    }
+            }
             break;
         }
         case PBG_CMD_TREE:

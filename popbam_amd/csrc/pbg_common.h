@@ -15,7 +15,7 @@
 #if defined(PBG_SLOW_NONET) || defined(PBG_ZNS_EXP) || defined(PBG_ZNS_SORT) || defined(PBG_ZNS_PRIO) || \
     defined(PBG_SCAN_WIDE_PASS) || defined(PBG_CALL_WAVES_PER_SIMD) || defined(PBG_SLOW_WG_PER_CU) ||      \
     defined(PBG_WIN_AHEAD) || defined(PBG_FAST_MAX) || defined(PBG_SYNTH_EXP) || defined(PBG_SCAN_EXP) || \
-    defined(PBG_SCAN_LDS_PAD) || defined(PBG_ZNS_GROUPS)
+    defined(PBG_SCAN_LDS_PAD) || defined(PBG_ZNS_GROUPS) || defined(PBG_XPNSL_PLAIN)
 #error "an experiment switch is defined: build variants with tools/variant.sh (-DPBG_EXPERIMENT=1)"
 #endif
 #define PBG_BUILD_KIND (PBG_BOUNDS_KIND)
@@ -419,6 +419,23 @@ struct NslArgs {
     int32_t *cens;             // [n_win * npops * max_sites * 2] or null
 };
 
+// window_xpnsl_kernel (pbg_window_xpnsl): the cross-population nSL tract sums per (window, population
+// pair).  One wave per chain and nsl's per-wave LDS layout, with both sides' sample pairs in one table:
+// the launcher sizes it from the largest C(n_i, 2) + C(n_j, 2) over the pairs and picks the waves per
+// workgroup (4, 2 or 1) that keep a launch within 64 KiB.  No workspace.
+struct XpnslArgs {
+    const pbg_window *wins;
+    int *err;
+    int32_t max_sites;
+    int32_t pairs_max, waves;  // set by the launcher: the largest table; chains per workgroup
+    uint32_t wave_bytes;       // set by the launcher: LDS per wave
+    int32_t *n_var;            // [n_win * n_pairs] or null
+    int32_t *row;              // [n_win * n_pairs * max_sites] or null
+    int32_t *m;                // [n_win * n_pairs * max_sites * 2] or null
+    int64_t *sl;               // [n_win * n_pairs * max_sites * 2] or null
+    int32_t *cens;             // [n_win * n_pairs * max_sites * 2] or null
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -571,5 +588,8 @@ hipError_t launch_window_rmin(int row_bytes, const DevParams &P, const void *row
 size_t nsl_wave_bytes(int row_bytes, int pairs_max);
 hipError_t launch_window_nsl(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                              NslArgs A, hipStream_t stream);
+// xpnsl_kernel.hip (dynamic LDS: waves * nsl_wave_bytes(row_bytes, the largest pair table))
+hipError_t launch_window_xpnsl(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                               XpnslArgs A, hipStream_t stream);
 
 }  // namespace pbg

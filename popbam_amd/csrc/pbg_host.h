@@ -63,6 +63,13 @@ struct WindowHost {
     std::vector<int32_t> nsl_n, nsl_pos, nsl_m, nsl_cens, nsl_pn;
     std::vector<int64_t> nsl_sl;
     int nsl_stride = 0;
+    // haplo --xpnsl (PBG_HAPLO_XPNSL in pbg_cmd.output): population pair p (i < j, lexicographic) has
+    // xp_n[p] pooled sites; site k at s = p * xp_stride + k: xp_pos[s] its contig position, 0-based,
+    // xp_m[2 * s + side], xp_sl[2 * s + side] and xp_cens[2 * s + side] the numbers of pbg_window_xpnsl;
+    // xp_pn[i] population i's size; empty when the caller has none (pbg_format)
+    std::vector<int32_t> xp_n, xp_pos, xp_m, xp_cens, xp_pn;
+    std::vector<int64_t> xp_sl;
+    int xp_stride = 0;
 };
 
 // sfs --dstat's triples of n_pops populations: all (i, j, k) with i < j and k neither, in

@@ -102,6 +102,7 @@ struct Options {
     int hfs = 0;                                                          // haplo --hfs (0: off)
     int rmin = 0;                                                         // ld --rmin (0: off)
     int nsl = 0;                                                          // haplo --nsl (0: off)
+    int xpnsl = 0;                                                        // haplo --xpnsl (0: off)
     unsigned int win_size = 0;
     long double het_prior = 0.0001L;                                      // -z: parsed, unused
 };
@@ -293,6 +294,8 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
         o.hfs = 1;   // extension: H1, H12, H123, H2H1, Hd and the class sizes of every population (any -o)
     if (cmd == "haplo" && std::find(argv.begin(), argv.end(), std::string("--nsl")) != argv.end())
         o.nsl = 1;   // extension: the per-site nSL of every population (any -o, also with --hfs)
+    if (cmd == "haplo" && std::find(argv.begin(), argv.end(), std::string("--xpnsl")) != argv.end())
+        o.xpnsl = 1;   // extension: the per-site XP-nSL of every population pair (any -o, also with --hfs and --nsl)
     if (cmd == "ld" && std::find(argv.begin(), argv.end(), std::string("--rmin")) != argv.end())
         o.rmin = 1;   // extension: Hudson and Kaplan's Rm and its intervals of every population (any -o)
     if (cmd == "ld" && tk.present('e')) o.min_freq = 2;
@@ -759,7 +762,8 @@ std::string run(const std::string &cmd, const std::vector<std::string> &argv, in
         hi = std::max(hi, lo);
         pbg_cmd c{};
         c.cmd = cmd_id(cmd);
-        c.output = o.output | (cmd == "ld" && o.rmin ? PBG_LD_RMIN : 0) | (cmd == "haplo" && o.nsl ? PBG_HAPLO_NSL : 0);
+        c.output = o.output | (cmd == "ld" && o.rmin ? PBG_LD_RMIN : 0) | (cmd == "haplo" && o.nsl ? PBG_HAPLO_NSL : 0) |
+                   (cmd == "haplo" && o.xpnsl ? PBG_HAPLO_XPNSL : 0);
         c.min_sites = o.min_sites;
         c.min_snps = o.min_snps;
         c.min_freq = o.min_freq;

@@ -165,7 +165,7 @@ int ensure_slot(pbg_ctx *c, pbg::StreamSlot &s, uint32_t chunk, size_t keys) {
     return PBG_OK;
 }
 
-// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin, haplo --nsl) is computed and copied
+// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin, haplo --nsl, haplo --xpnsl) is computed and copied
 // to the host a block of windows at a time, so that its device buffer and its host copy stay at
 // kStage bytes each however many windows and populations there are.
 constexpr size_t kStage = 64u << 20;
@@ -541,6 +541,42 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
                   {h_nsl.data(), d_sl, slots * 16}};
         return pbg_window_nsl(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
     };
+    // haplo --xpnsl: the XP-nSL kernel over the same windows, per population pair (its columns follow
+    // --nsl's), staged as --nsl is: a block runs once for the counts alone, then, when some count is not
+    // 0, again with max_sites = the block's largest count.  Fewer than two populations: no pair, no call.
+    const size_t xP = (size_t)np * (np - 1) / 2;
+    const bool xpnsl = cmd->cmd == PBG_CMD_HAPLO && (cmd->output & PBG_HAPLO_XPNSL) && xP > 0;
+    constexpr size_t kXpSite = 16 + 8 + 8 + 4;   // sl, cens, m, row: bytes per slot
+    WinBlocks xb = win_blocks(xpnsl, nw, xP * (4 + kXpSite * kNslGuess));
+    std::vector<int32_t> h_xn, h_xrow, h_xm, h_xcens;
+    std::vector<int64_t> h_xsl;
+    size_t xS = 0;   // the block's stride: slots per (window, pair)
+    auto xpnsl_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t got = (size_t)cnt * xP;
+        int xrc = grow(c, c->sb.xpnsl, al((size_t)xb.size * xP * 4));
+        if (xrc) return xrc;
+        const pbg_xpnsl_opts nopt{0, 0};
+        const pbg_xpnsl_out nout{(int32_t *)c->sb.xpnsl.d, nullptr, nullptr, nullptr, nullptr};
+        if ((xrc = pbg_window_xpnsl(c, d_rows, dsites, d_win + first, cnt, &nopt, &nout, s))) return xrc;
+        h_xn.resize(got);
+        HIPCHK(c, d2h(h_xn.data(), nout.n_var, got * 4));
+        HIPCHK(c, hipStreamSynchronize(s));
+        xS = (size_t)std::max(0, *std::max_element(h_xn.begin(), h_xn.end()));
+        const size_t slots = got * xS;
+        h_xrow.resize(slots);
+        h_xm.resize(slots * 2);
+        h_xcens.resize(slots * 2);
+        h_xsl.resize(slots * 2);
+        if (xS == 0) return PBG_OK;
+        if ((xrc = grow(c, c->sb.xpnsl_sites, slots * kXpSite))) return xrc;
+        int64_t *d_sl = (int64_t *)c->sb.xpnsl_sites.d;   // the widest first: every part stays aligned
+        int32_t *d_cens = (int32_t *)(d_sl + slots * 2), *d_m = d_cens + slots * 2, *d_row = d_m + slots * 2;
+        const pbg_xpnsl_opts sopt{(int32_t)xS, 0};
+        const pbg_xpnsl_out sout{nullptr, d_row, d_m, d_sl, d_cens};
+        copies = {{h_xrow.data(), d_row, slots * 4}, {h_xm.data(), d_m, slots * 8}, {h_xcens.data(), d_cens, slots * 8},
+                  {h_xsl.data(), d_sl, slots * 16}};
+        return pbg_window_xpnsl(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
@@ -587,6 +623,19 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             wh.nsl_sl = slice(h_nsl, e0 * nS * 2, per * 2);
             wh.nsl_pn.assign(c->dp.pop_n, c->dp.pop_n + np);
             wh.nsl_stride = (int)nS;
+        }
+        if (xpnsl) {
+            if (i >= xb.w1 && (rc = next_block(c, s, xb, i, nw, xpnsl_call))) return rc;
+            const size_t e0 = (size_t)(i - xb.w0) * xP, per = xP * xS;
+            wh.xp_n = slice(h_xn, e0, xP);
+            wh.xp_pos = slice(h_xrow, e0 * xS, per);
+            for (int32_t &x : wh.xp_pos)
+                if (x >= 0) x += (int32_t)dpos0;   // row -> contig position
+            wh.xp_m = slice(h_xm, e0 * xS * 2, per * 2);
+            wh.xp_cens = slice(h_xcens, e0 * xS * 2, per * 2);
+            wh.xp_sl = slice(h_xsl, e0 * xS * 2, per * 2);
+            wh.xp_pn.assign(c->dp.pop_n, c->dp.pop_n + np);
+            wh.xp_stride = (int)xS;
         }
         wh.beg = win[i].first;
         wh.end = win[i].second;
@@ -635,7 +684,7 @@ void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
     for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs, &b.rmin, &b.rmin_cuts, &b.nsl,
-                            &b.nsl_sites})
+                            &b.nsl_sites, &b.xpnsl, &b.xpnsl_sites})
         if (x->d) (void)hipFree(x->d);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

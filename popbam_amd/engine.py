@@ -61,6 +61,8 @@ class _Cmd:
             c.output |= _lib.PBG_LD_RMIN
         if o.cmd == "haplo" and o.nsl:
             c.output |= _lib.PBG_HAPLO_NSL
+        if o.cmd == "haplo" and o.xpnsl:
+            c.output |= _lib.PBG_HAPLO_XPNSL
         c.outidx = 0
         if o.flag & opt.BAM_OUTGROUP and o.cmd in ("sfs", "diverge", "snp"):   # nucdiv sets the flag, never reads -p
             idx = [i for i, s in enumerate(sm.samples) if s == o.outgroup]

@@ -64,6 +64,7 @@ class Options:
     hfs: int = 0           # haplo --hfs: append the haplotype frequency spectrum and Garud's H (0: off)
     rmin: int = 0          # ld --rmin: append Hudson and Kaplan's Rm and its intervals (0: off)
     nsl: int = 0           # haplo --nsl: append the per-site nSL of every population (0: off)
+    xpnsl: int = 0         # haplo --xpnsl: append the per-site XP-nSL of every population pair (0: off)
     errors: list = field(default_factory=list)
 
 
@@ -209,6 +210,8 @@ def parse_args(cmd: str, argv: list[str]) -> Options:
         o.hfs = 1   # extension: append H1, H12, H123, H2H1, Hd and the class sizes of every population (any -o)
     if cmd == "haplo" and "--nsl" in argv:
         o.nsl = 1   # extension: append the per-site nSL of every population (any -o, also with --hfs)
+    if cmd == "haplo" and "--xpnsl" in argv:
+        o.xpnsl = 1   # extension: append the per-site XP-nSL of every population pair (any -o, also with --hfs and --nsl)
     if cmd == "ld" and "--rmin" in argv:
         o.rmin = 1   # extension: append Rm and its intervals of every population (any -o)
     if cmd == "ld" and "e" in present:

@@ -368,6 +368,46 @@ class Nsl:
         return cls(hp.ctx, hp.n_win, max_sites, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
+class Xpnsl:
+    """pbg_window_xpnsl: the cross-population nSL tract sums per window and population pair (i < j,
+    lexicographic).  Owns the device arrays -- n_var[n_win, n_pairs] (int32) and, with max_sites > 0,
+    row[n_win, n_pairs, max_sites] (int32), m and cens[n_win, n_pairs, max_sites, 2] (int32) and
+    sl[n_win, n_pairs, max_sites, 2] (int64), the last index the side -- and runs on a HotPath's rows and
+    windows, or on any rows tensor with a window list.  max_sites = 0 is the count-only call."""
+
+    NAMES = ("n_var", "row", "m", "sl", "cens")
+
+    def __init__(self, ctx: _lib.Context, n_win: int, max_sites: int = 0, device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        np_, ms = ctx.params.n_pops, max(max_sites, 0)
+        self.n_pairs = npr = np_ * (np_ - 1) // 2
+        self.opts = _lib.PbgXpnslOpts(max_sites, 0)
+        self.n_var = torch.zeros((n_win, npr), dtype=torch.int32, device=device)
+        self.row = torch.zeros((n_win, npr, ms), dtype=torch.int32, device=device)
+        self.m = torch.zeros((n_win, npr, ms, 2), dtype=torch.int32, device=device)
+        self.sl = torch.zeros((n_win, npr, ms, 2), dtype=torch.int64, device=device)
+        self.cens = torch.zeros((n_win, npr, ms, 2), dtype=torch.int32, device=device)
+        per_site = [_ptr(t) if max_sites > 0 else None for t in (self.row, self.m, self.sl, self.cens)]
+        self.out = _lib.PbgXpnslOut(_ptr(self.n_var), *per_site)
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_xpnsl(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                             C.byref(self.opts), C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_xpnsl")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", max_sites: int = 0, stream=None) -> "Xpnsl":
+        """The tract sums of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, max_sites, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 

@@ -1,5 +1,5 @@
 """The window passes on one resident batch, for one or more built checkouts:
-`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin,nsl] [--tree DIR]... [--sites 50000000]
+`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin,nsl,xpnsl] [--tree DIR]... [--sites 50000000]
 [--samples 12] [--pops 2] [--window 10000] [--depth 10] [--reps 25] [--seed 0xC0FFEE02] [--out FILE]`.
 
 The BASELINE configs[2] shape by default: 50 Msites x 12 samples x 2 populations, 10 kb reference
@@ -16,9 +16,13 @@ windows:
   rmin   pbg_window_rmin with rmin and n_var alone, and rmin_cuts with max_cuts = 64 and all three
   nsl    pbg_window_nsl count-only (max_sites = 0) as nsl_nvar, and nsl, the full call with all five
          outputs and max_sites = the largest count nsl_nvar found
-A tree without one of the calls cannot run that pass; rmin and nsl alone are skipped there (and named
-in `skipped`): rmin's yardstick is the decay_1x1 of the tree before it, nsl's is that tree's rmin, and
-with two trees the comparison sets nsl_nvar against the first tree's rmin and gives nsl's ratio to it.
+  xpnsl  pbg_window_xpnsl count-only as xpnsl_nvar, and xpnsl, the full call with all five outputs and
+         max_sites = the largest count xpnsl_nvar found.  Needs --pops 2 or more; skipped below that.
+A tree without one of the calls cannot run that pass; rmin, nsl and xpnsl alone are skipped there (and
+named in `skipped`): rmin's yardstick is the decay_1x1 of the tree before it, nsl's is that tree's rmin,
+and with two trees of which the first has no nsl the comparison sets nsl_nvar against the first
+tree's rmin and gives nsl's ratio to it (when both trees have nsl, it is compared pass against pass
+like every other); xpnsl's yardsticks are the first tree's nsl_nvar and nsl, and the comparison gives the ratios.
 
 Every --tree (default: this checkout) is measured in a fresh child process that imports that tree's
 popbam_amd package and library; this process never touches the GPU.  Two or more trees are measured
@@ -37,7 +41,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin", "nsl")
+PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin", "nsl", "xpnsl")
 SHAPE = ("samples", "pops", "sites", "window", "depth", "reps", "seed")
 
 
@@ -99,6 +103,17 @@ def child(a, passes):
         extra["nsl_sites"] = int(cnt.n_var.sum().item())
         if extra["nsl_max_sites"] > 0:
             runs["nsl"] = on_rows(workload.Nsl(ctx, hp.n_win, extra["nsl_max_sites"]))
+    if "xpnsl" in passes and (not hasattr(workload, "Xpnsl") or a.pops < 2):
+        skipped.append("xpnsl")   # a tree from before the call: its nsl is the yardstick
+    elif "xpnsl" in passes:
+        cnt = workload.Xpnsl(ctx, hp.n_win)
+        runs["xpnsl_nvar"] = on_rows(cnt)
+        cnt(hp.rows, hp.wins, sites)
+        ctx.sync_check()
+        extra["xpnsl_max_sites"] = int(cnt.n_var.max().item())
+        extra["xpnsl_sites"] = int(cnt.n_var.sum().item())
+        if extra["xpnsl_max_sites"] > 0:
+            runs["xpnsl"] = on_rows(workload.Xpnsl(ctx, hp.n_win, extra["xpnsl_max_sites"]))
     for f in runs.values():   # warm: plans, workspace, tables, code objects
         f()
         f()
@@ -135,7 +150,8 @@ def compare(first, second):
         margin = max(max(a) - min(a), 0.02 * base)
         cmp[key[:-len("_ms_median")]] = {"first_ms": round(base, 4), "second_ms": round(new, 4), "margin_ms": round(margin, 4),
                                          "ok": new <= base + margin}
-    if "rmin_ms_median" in first[0] and "nsl_nvar_ms_median" in second[0]:   # nsl against the first tree's rmin
+    if "rmin_ms_median" in first[0] and "nsl_nvar_ms_median" in second[0] and "nsl_nvar_ms_median" not in first[0]:
+        # nsl against the rmin of a first tree that has no nsl of its own
         a = [r["rmin_ms_median"] for r in first]
         base = statistics.mean(a)
         margin = max(max(a) - min(a), 0.02 * base)
@@ -144,6 +160,11 @@ def compare(first, second):
                 new = statistics.mean(r[nm + "_ms_median"] for r in second)
                 cmp[nm] = {"first_rmin_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
         cmp["nsl_nvar"].update(margin_ms=round(margin, 4), ok=cmp["nsl_nvar"]["second_ms"] <= base + margin)
+    for nm, yard in (("xpnsl_nvar", "nsl_nvar"), ("xpnsl", "nsl")):   # xpnsl against the first tree's nsl
+        if yard + "_ms_median" in first[0] and nm + "_ms_median" in second[0]:
+            base = statistics.mean(r[yard + "_ms_median"] for r in first)
+            new = statistics.mean(r[nm + "_ms_median"] for r in second)
+            cmp[nm] = {f"first_{yard}_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
     return cmp
 
 
