@@ -434,8 +434,10 @@ void do_sfs(Out &o, const orc_params *p, const orc_cmd *c, const Window &W, cons
                 fwh[i] += sfs[j] * ((1.0 / a1[n]) - ((double)j / (n - 1)));
             }
             td[i] /= std::sqrt(e1[n] * S + e2[n] * S * (S - 1));
+            // int * int as in the reference (pop_sfs.cpp:277): wraps past 46,341 sites, spelled out
+            const int ss1 = (int)((unsigned)S * (unsigned)(S - 1));
             fwh[i] /= std::sqrt(((n - 2) * (S / a1[n]) / (6.0 * (n - 1))) +
-                                ((S * (S - 1) / ((a1[n] * a1[n]) + a2[n])) *
+                                ((ss1 / ((a1[n] * a1[n]) + a2[n])) *
                                  (18.0 * (n * n) * (3.0 * n + 2.0) * a2[n + 1] - (88.0 * n * n * n + 9.0 * (n * n) - 13.0 * n + 6.0)) /
                                  (9.0 * n * ((n - 1) * (n - 1)))));
         } else {

@@ -357,8 +357,12 @@ __global__ __launch_bounds__(64) void window_stats_kernel(DevParams P, DevTables
                 fwh += sfs[j] * ((1.0 / a1) - ((double)j / (nn - 1)));
             }
             td /= sqrt(e1 * S_i + e2 * S_i * (S_i - 1));
+            // the reference multiplies num_snps * (num_snps - 1) as int before it divides: past 46,341
+            // sites the product wraps (x86 imul), H's variance turns negative or small and the reference
+            // prints that; the wrap is spelled out here, where signed overflow would be undefined
+            const int ss1 = (int)((unsigned)S_i * (unsigned)(S_i - 1));
             fwh /= sqrt(((nn - 2) * (S_i / a1) / (6.0 * (nn - 1))) +
-                        ((S_i * (S_i - 1) / ((a1 * a1) + a2)) *
+                        ((ss1 / ((a1 * a1) + a2)) *
                          (18.0 * (nn * nn) * (3.0 * nn + 2.0) * a2n1 - (88.0 * nn * nn * nn + 9.0 * (nn * nn) - 13.0 * nn + 6.0)) /
                          (9.0 * nn * ((nn - 1) * (nn - 1)))));
         } else {

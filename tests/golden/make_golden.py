@@ -150,6 +150,13 @@ SCENARIOS = {
     "g18_64s4p": dict(seed=1818, L=8000, samples=_samples(64, ["q1", "q2", "q3", "q4"]), step=10, mu=0.03,
                       cmds=_std_cmds("1", [["nucdiv", "-w", "4"], ["sfs", "-w", "4"], ["ld", "-w", "4"],
                                            ["haplo", "-w", "2", "-o", "2"]])),
+    # G19 / G20: haplotype structure (founders): samples of a population share haplotypes, columns repeat
+    # G19: 24 samples in 3 populations, 3 founders redrawn every 1500 sites
+    "g19_founders24": dict(seed=1919, L=11000, samples=_samples(24, ["pa", "pb", "pc"]), step=14, mu=0.05,
+                           founders=(3, 1500), err=0.0005, cmds=_std_cmds("1", [["tree", "-w", "1"]])),
+    # G20: 64 samples in 2 populations of 32, 4 founders redrawn every 1300 sites
+    "g20_founders64": dict(seed=2020, L=4100, samples=_samples(64, ["popA", "popB"]), step=14, mu=0.06,
+                           founders=(4, 1300), err=0.0005, cmds=_std_cmds("1", [["tree", "-w", "1"]])),
 }
 
 
@@ -167,10 +174,20 @@ def simulate(sc):
     ref_idx = np.array([BASES.index(c) for c in refseq])
     geno = np.repeat(ref_idx[:, None, None], n, axis=1).repeat(2, axis=2)  # L x n x 2
     snp = rng.rand(L) < sc.get("mu", 0.02)
+    # founders=(F, stretch): haplotype structure.  F founder haplotypes are drawn per site at the
+    # scenario's frequency, every sample is homozygous for one founder, and the founder of each sample
+    # is redrawn every `stretch` sites; reads, errors and qualities as without the option
+    founders = sc.get("founders")
+    src = None
     for p in np.nonzero(snp)[0]:
         d = (ref_idx[p] + rng.randint(1, 4)) % 4
         f = rng.uniform(0.5, 1.0) if sc.get("freq_hi") else rng.uniform(0.0, 1.0)
-        alle = rng.rand(n, 2) < f
+        if founders:
+            if src is None or p // founders[1] != src[0]:
+                src = (p // founders[1], rng.randint(0, founders[0], n))
+            alle = np.repeat((rng.rand(founders[0]) < f)[src[1]][:, None], 2, axis=1)
+        else:
+            alle = rng.rand(n, 2) < f
         geno[p][alle] = d
         if rng.rand() < sc.get("multi", 0.0):
             d2 = (d + rng.randint(1, 3)) % 4

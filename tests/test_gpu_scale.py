@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import harness
+from window_helpers import oracle_text as _oracle_text, window_text as _window_text
 
 pytestmark = pytest.mark.gpu
 
@@ -237,54 +238,6 @@ def test_stream_soft_masked_matches_oracle(gpu_lib, n, kw):
     got = rows.cpu().numpy()
     assert np.array_equal(got, expect)
     ctx.close()
-
-
-def _window_text(ctx, params, hp, cmd_id, output, windows, min_freq=1, jc=0, min_snps=10, flag_sub=False):
-    """Format the GPU window outputs with the library's print_<stat> (pbg_format)."""
-    from popbam_amd import _lib
-    n, np_ = params.n_samples, params.n_pops
-    host = {k: v.cpu().numpy() for k, v in hp.out.t.items()}
-    o = _lib.PbgWindowOut()
-    for k in [f for f, _ in _lib.PbgWindowOut._fields_]:
-        setattr(o, k, host[k].ctypes.data)
-    c = _lib.PbgCmd()
-    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq, c.jc = cmd_id, output, 10, min_snps, min_freq, jc
-    c.chr_name = b"chr1"
-    sn = (C.c_char_p * n)(*[f"s{i}".encode() for i in range(n)])
-    pn = (C.c_char_p * np_)(*[f"p{i}".encode() for i in range(np_)])
-    c.sample_names = C.cast(sn, C.POINTER(C.c_char_p))
-    c.pop_names = C.cast(pn, C.POINTER(C.c_char_p))
-    c.refid = b"ref"
-    wb = np.array([a for a, _ in windows], np.int32)
-    we = np.array([b for _, b in windows], np.int32)
-    cap = 1 << 24
-    buf = C.create_string_buffer(cap)
-    need = C.c_size_t()
-    r = ctx.lib.pbg_format(ctx.h, C.byref(c), C.byref(o), len(windows), wb.ctypes.data, we.ctypes.data, buf, cap,
-                           C.byref(need))
-    ctx.check(r, "pbg_format")
-    return buf.value.decode()
-
-
-def _oracle_text(params, types, flags, cmd_id, output, windows, min_freq=1, jc=0, min_snps=10):
-    p = harness.oracle_params_from(params)
-    c = harness.OrcCmd()
-    n, np_ = params.n_samples, params.n_pops
-    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq, c.jc = cmd_id, output, 10, min_snps, min_freq, jc
-    c.chr_name = b"chr1"
-    sn = (C.c_char_p * n)(*[f"s{i}".encode() for i in range(n)])
-    pn = (C.c_char_p * np_)(*[f"p{i}".encode() for i in range(np_)])
-    c.sample_names = C.cast(sn, C.POINTER(C.c_char_p))
-    c.pop_names = C.cast(pn, C.POINTER(C.c_char_p))
-    c.refid = b"ref"
-    wb = np.array([a for a, _ in windows], np.int32)
-    we = np.array([b for _, b in windows], np.int32)
-    cap = 1 << 24
-    buf = C.create_string_buffer(cap)
-    r = harness.oracle().orc_windows_from_sites(C.byref(p), C.byref(c), types.ctypes.data, flags.ctypes.data,
-                                                len(windows), wb.ctypes.data, we.ctypes.data, buf, cap)
-    assert r >= 0
-    return buf.value.decode()
 
 
 STATS = [  # (PBG_S_* flag, popbam_func_t, -o, min_freq, jc)

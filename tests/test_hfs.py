@@ -16,7 +16,7 @@ import pytest
 import fixtures
 import harness
 from window_helpers import _argv, _arrays, bits, _blocks, _native, _wins_tensor
-from window_helpers import PARTIAL_WORD_CASES, partial_rows
+from window_helpers import PARTIAL_WORD_CASES, oracle_text, partial_rows
 from popbam_amd import cli
 from popbam_amd import options as opt
 
@@ -197,24 +197,7 @@ def test_hfs_option_parses():
 
 
 def _oracle_text(params, types, flags, cmd_id, output, windows):
-    p = harness.oracle_params_from(params)
-    c = harness.OrcCmd()
-    n, np_ = params.n_samples, params.n_pops
-    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq, c.jc = cmd_id, output, 0, 10, 1, 0
-    c.chr_name = b"chr1"
-    sn = (C.c_char_p * n)(*[f"s{i}".encode() for i in range(n)])
-    pn = (C.c_char_p * np_)(*[f"p{i}".encode() for i in range(np_)])
-    c.sample_names = C.cast(sn, C.POINTER(C.c_char_p))
-    c.pop_names = C.cast(pn, C.POINTER(C.c_char_p))
-    c.refid = b"ref"
-    wb = np.array([a for a, _ in windows], np.int32)
-    we = np.array([b for _, b in windows], np.int32)
-    cap = 1 << 22
-    buf = C.create_string_buffer(cap)
-    r = harness.oracle().orc_windows_from_sites(C.byref(p), C.byref(c), types.ctypes.data, flags.ctypes.data,
-                                                len(windows), wb.ctypes.data, we.ctypes.data, buf, cap)
-    assert r >= 0
-    return buf.value.decode()
+    return oracle_text(params, types, flags, cmd_id, output, windows, min_sites=0)
 
 
 def _one_population(n):

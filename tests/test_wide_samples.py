@@ -7,11 +7,14 @@ order and their samples' order, a fifth population of copies of samples 0..31 is
 after the second, so populations 2 and 3 move into the masks' second word.  Copies call
 exactly as their originals, so the counted and segregating positions do not change, and every
 statistic below that depends on a population's own samples (and, for dxy, on the order of two
-populations' samples) equals the reference's golden value for that population.
+populations' samples) equals the reference's golden value for that population.  The same is done
+with g20_founders64 (two populations of 32 with haplotype structure: samples of a population share
+haplotypes and columns repeat); there the copies go between the two, so the second moves into
+the second word.
 
 Not invariant under the embedding, so compared only GPU-vs-oracle (test_gpu_* below):
 Wall's B/Q (last_type is shared across populations, Appendix A.9, and the copies are
-variable wherever populations 0/1 are) and snp (one column per sample).
+variable wherever populations 0/1 are), snp (one column per sample) and tree (one taxon per sample).
 """
 import numpy as np
 import pytest
@@ -19,23 +22,30 @@ import pytest
 import fixtures
 import harness
 
-CASE = "g18_64s4p"
-INVARIANT = [a for a in (c["args"] for c in fixtures.load_case(CASE)["meta"]["cases"])
-             if not (a[0] == "snp" or (a[0] == "ld" and "-o" in a and a[a.index("-o") + 1] == "2"))]
+CASES = {"g18_64s4p": 1, "g20_founders64": 0}   # case -> the population the copies are inserted after
 
 
-def _golden(args):
-    for c in fixtures.load_case(CASE)["meta"]["cases"]:
+def _id(case, a):
+    return " ".join(a) if case == "g18_64s4p" else case + " " + " ".join(a)
+
+
+INVARIANT = [pytest.param(case, a, id=_id(case, a)) for case in CASES
+             for a in (c["args"] for c in fixtures.load_case(case)["meta"]["cases"])
+             if not (a[0] in ("snp", "tree") or (a[0] == "ld" and "-o" in a and a[a.index("-o") + 1] == "2"))]
+
+
+def _golden(case, args):
+    for c in fixtures.load_case(case)["meta"]["cases"]:
         if c["args"] == args:
-            return fixtures.golden_text(CASE, c["stdout"]), c["region"]
+            return fixtures.golden_text(case, c["stdout"]), c["region"]
     raise KeyError(args)
 
 
-@pytest.mark.parametrize("args", INVARIANT, ids=[" ".join(a) for a in INVARIANT])
-def test_wide_oracle_reproduces_the_reference_on_embedded_populations(args):
-    gold, region = _golden(args)
-    st = harness.WideSetup(CASE, args, region)
-    assert st.sm.n == 96 and max(i for i, p in enumerate(st.sm.sample_pop) if p == 4) == 95
+@pytest.mark.parametrize("case,args", INVARIANT)
+def test_wide_oracle_reproduces_the_reference_on_embedded_populations(case, args):
+    gold, region = _golden(case, args)
+    st = harness.WideSetup(case, args, region, after=CASES[case])
+    assert st.sm.n == 96 and max(i for i, p in enumerate(st.sm.sample_pop) if p == len(st.sm.pops) - 1) == 95
     ours = harness.oracle_run(st)
     g, o = harness.labelled_values(gold), harness.labelled_values(ours)
     assert len(gold.splitlines()) == len(ours.splitlines())
@@ -91,18 +101,20 @@ def test_wide_calls_split_into_independent_samples():
     assert int((flags & 4 > 0).sum()) > 50
 
 
-GPU_ARGS = [c["args"] for c in fixtures.load_case(CASE)["meta"]["cases"]] + [
-    ["snp", "-o", "1"], ["snp", "-o", "2", "-w", "1"], ["tree", "-w", "1"], ["tree", "-w", "1", "-d", "jc"]]
+EXTRA_ARGS = [["snp", "-o", "1"], ["snp", "-o", "2", "-w", "1"], ["tree", "-w", "1"], ["tree", "-w", "1", "-d", "jc"]]
+GPU_ARGS = [pytest.param(case, a, id=_id(case, a)) for case in CASES
+            for a in [c["args"] for c in fixtures.load_case(case)["meta"]["cases"]]
+            + [x for x in EXTRA_ARGS if x not in [c["args"] for c in fixtures.load_case(case)["meta"]["cases"]]]]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("copies", [32, 62])
-@pytest.mark.parametrize("args", GPU_ARGS, ids=[" ".join(a) for a in GPU_ARGS])
-def test_gpu_wide_run_matches_wide_oracle(gpu_lib, args, copies):
+@pytest.mark.parametrize("case,args", GPU_ARGS)
+def test_gpu_wide_run_matches_wide_oracle(gpu_lib, case, args, copies):
     """pbg_run (key batch -> call kernels -> statistics -> TSV) with 96 and 126 samples: the
     whole text equals the 128-bit oracle's (pinned above), Wall and snp included."""
     from popbam_amd import engine
-    st = harness.WideSetup(CASE, args, "chr1", n_copies=copies)
+    st = harness.WideSetup(case, args, "chr1", n_copies=copies, after=CASES[case])
     assert st.sm.n == 64 + copies
     ours = engine.run_command(st.opts, st.sm, st.chr, st.beg, st.end, st.kbatch, refid=st.refid)
     orc = harness.oracle_run(st)

@@ -1,6 +1,10 @@
 """Helpers shared by the tests of the per-window side tables (test_ld_decay.py, test_jsfs.py,
 test_dstat.py, test_hfs.py): bit arithmetic for the checkers, crafted inputs, and the native
-command line.  The checkers themselves (`ref_*`) stay with their tests."""
+command line.  The checkers themselves (`ref_*`) stay with their tests.  Also the two text
+printers of the pbg_window_stats tests (test_gpu_scale.py, test_window_gather.py, test_window_edges.py,
+test_hfs.py): window_text (pbg_format over the device outputs) and oracle_text (the oracle's windows
+over given sites)."""
+import ctypes as C
 import os
 import subprocess
 
@@ -8,6 +12,7 @@ import numpy as np
 import pytest
 
 import fixtures
+import harness
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(REPO, "bin", "popbam")
@@ -92,3 +97,58 @@ def partial_rows(n, words):
         return 64 * 5 + 3, []
     R = 16 // (2 if n <= 14 else 4 if n <= 30 else 8 if n <= 62 else 16)
     return words * R + 3, [(256 * R - 1, 256 * R + 1)]
+
+
+def _names(c, n, np_):
+    """chr1 / s<i> / p<i> / ref into a command struct; the arrays returned must outlive the call."""
+    c.chr_name = b"chr1"
+    sn = (C.c_char_p * n)(*[f"s{i}".encode() for i in range(n)])
+    pn = (C.c_char_p * np_)(*[f"p{i}".encode() for i in range(np_)])
+    c.sample_names = C.cast(sn, C.POINTER(C.c_char_p))
+    c.pop_names = C.cast(pn, C.POINTER(C.c_char_p))
+    c.refid = b"ref"
+    return sn, pn
+
+
+def window_text(ctx, params, hp, cmd_id, output, windows, min_freq=1, jc=0, min_snps=10, outidx=0,
+                min_sites=10):
+    """Format the GPU window outputs (`hp.out.t`, a workload.WindowOutputs' tensors) with the
+    library's print_<stat> (pbg_format)."""
+    from popbam_amd import _lib
+    host = {k: v.cpu().numpy() for k, v in hp.out.t.items()}
+    o = _lib.PbgWindowOut()
+    for k in [f for f, _ in _lib.PbgWindowOut._fields_]:
+        setattr(o, k, host[k].ctypes.data)
+    c = _lib.PbgCmd()
+    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq, c.jc = cmd_id, output, min_sites, min_snps, min_freq, jc
+    c.outidx = outidx
+    keep = _names(c, params.n_samples, params.n_pops)
+    wb = np.array([a for a, _ in windows], np.int32)
+    we = np.array([b for _, b in windows], np.int32)
+    cap = 1 << 24
+    buf = C.create_string_buffer(cap)
+    need = C.c_size_t()
+    r = ctx.lib.pbg_format(ctx.h, C.byref(c), C.byref(o), len(windows), wb.ctypes.data, we.ctypes.data, buf, cap,
+                           C.byref(need))
+    ctx.check(r, "pbg_format")
+    del keep
+    return buf.value.decode()
+
+
+def oracle_text(params, types, flags, cmd_id, output, windows, min_freq=1, jc=0, min_snps=10, outidx=0, min_sites=10):
+    """The oracle's text of one command over the windows of given sites (orc_windows_from_sites)."""
+    p = harness.oracle_params_from(params)
+    c = harness.OrcCmd()
+    c.cmd, c.output, c.min_sites, c.min_snps, c.min_freq, c.jc = cmd_id, output, min_sites, min_snps, min_freq, jc
+    c.outidx = outidx
+    keep = _names(c, params.n_samples, params.n_pops)
+    wb = np.array([a for a, _ in windows], np.int32)
+    we = np.array([b for _, b in windows], np.int32)
+    types, flags = np.ascontiguousarray(types), np.ascontiguousarray(flags)
+    cap = 1 << 24
+    buf = C.create_string_buffer(cap)
+    r = harness.oracle().orc_windows_from_sites(C.byref(p), C.byref(c), types.ctypes.data, flags.ctypes.data,
+                                                len(windows), wb.ctypes.data, we.ctypes.data, buf, cap)
+    assert r >= 0
+    del keep
+    return buf.value.decode()
