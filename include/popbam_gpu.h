@@ -476,6 +476,59 @@ typedef struct {               /* DEVICE arrays, caller-allocated, NULL = not wa
 int pbg_window_xpnsl(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins,
                      uint32_t n_win, const pbg_xpnsl_opts *opts, const pbg_xpnsl_out *out, void *stream);
 
+/* The exact sample-by-sample difference matrix of a window, and Hudson's nearest-neighbour statistic Snn
+ * (Hudson 2000) with its permutation test per window and group of populations (an extension; the
+ * reference has no counterpart).
+ *   diff   For window [beg, end) and samples u < v, d(u, v) is the number of the window's rows with the
+ *          segregating bit whose bits u and v differ: a plain int32 with no 16-bit wrap (tree_diff keeps
+ *          the reference's), stored at w * n(n-1)/2 + q, q = u (2n - u - 1) / 2 + (v - u - 1).
+ *   groups A group is a set of at least two populations (bit i of groups[e] = population i belongs).  Its
+ *          members are the samples of those populations in ascending sample id, A_0 < ... < A_{N-1},
+ *          each labelled with its population.
+ *   snn    For member a: m_a = min over b != a of d(A_a, A_b), T_a = #{b != a : d = m_a} and
+ *          W_a = #{b != a : d = m_a and label(b) = label(a)}; T_a does not depend on the labels.  For
+ *          t = 1 .. N-1, S_t = sum of W_a over the members with T_a = t, and sum = sum over t of
+ *          (double)S_t / (double)t: one sequential double sum from +0.0 in ascending t, IEEE division, no
+ *          contraction (terms with S_t = 0 may be skipped).  snn[w * n_groups + e] = sum / (double)N.
+ *   near   near[2 (w * n_groups + e)] = sum of W_a, near[.. + 1] = sum of T_a: exact integers.
+ *   ge     Permutation r = 0 .. n_perms-1 of window w: with K = (uint32_t)(key0 + (uint32_t)wins[w].beg),
+ *          G = 0x9E3779B97F4A7C15, arithmetic mod 2^64 and
+ *            mix(z): z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; z ^ z>>31
+ *          base = mix(seed<<32 | K), pr = mix(base + (r+1) G) and key(s) = mix(pr + (s+1) G) for the
+ *          absolute sample id s.  Within a group member a has rank rho(a) in the order by (key(A_a), A_a)
+ *          ascending, and its permuted label is the true label of member rho(a): a group of a subset of
+ *          the populations sees the order induced by the same keys (the group index is not hashed).
+ *          sum_r is formed exactly as sum, and ge[w * n_groups + e] is the number of r with
+ *          sum_r >= sum (double comparison); the permutation p-value is (ge + 1) / (n_perms + 1).  With
+ *          n_perms = 0, ge is zero.
+ * A window without a segregating row has d = 0 everywhere, so every member ties with every other:
+ * snn = sum of n_i (n_i - 1) over the group's populations / (N (N - 1)) by the formula above, and
+ * ge = n_perms.  beg >= end gives zero differences.  A window outside [0, n_rows] is not read: it gives
+ * zero differences and the next pbg_check returns PBG_E_RANGE.  Everything is integers and order-fixed
+ * doubles: two runs give the same bytes, and a window's result depends on key0 + beg, the rows and the
+ * options only, not on its place in the list.  A NULL member of pbg_snn_out is skipped; with diff NULL and
+ * groups asked for the matrix lives in a buffer of the context, which such calls share: keep them on one
+ * stream.  n_groups = 0 is the difference matrix alone, valid for one population too.  Asynchronous; no workspace and no plan; the group
+ * list is copied to the device once per content.  pbg_snn_chunks is the number of permutation chunks the
+ * call's second kernel runs per (window, group) -- the host's choice, for tests and timing.  PBG_E_ARG for
+ * a null ctx, rows, wins, opts or out, n_groups outside 0..PBG_SNN_MAX_GROUPS, n_perms outside
+ * 0..PBG_SNN_MAX_PERMS, groups NULL with n_groups > 0, a group with fewer than two populations or with a
+ * bit at or above n_pops, and (with groups) a context whose pop_n[i] is not the number of samples in
+ * pop_mask[i]; n_win == 0 returns PBG_OK. */
+#define PBG_SNN_MAX_GROUPS 4096
+#define PBG_SNN_MAX_PERMS  65535
+typedef struct { const uint64_t *groups;   /* HOST array [n_groups]: bit i = population i belongs to the group */
+                 int32_t n_groups, n_perms; uint32_t seed, key0; } pbg_snn_opts;
+typedef struct {            /* DEVICE arrays, caller-allocated, NULL = not wanted */
+    int32_t *diff;          /* [n_win * n(n-1)/2]   */
+    double  *snn;           /* [n_win * n_groups]   */
+    int32_t *near;          /* [n_win * n_groups * 2] */
+    int32_t *ge;            /* [n_win * n_groups]   */
+} pbg_snn_out;
+int pbg_window_snn(pbg_ctx *ctx, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                   const pbg_snn_opts *opts, const pbg_snn_out *out, void *stream);
+int pbg_snn_chunks(uint32_t n_win, int32_t n_groups, int32_t n_perms);
+
 /* Waits for `stream` and reports what the kernels flagged since the last check: PBG_OK;
  * PBG_E_BATCH when a pileup batch's block_off disagreed with its k[] (the affected blocks
  * were written as uncounted rows and never read past their key range); PBG_E_RANGE when the
@@ -495,6 +548,9 @@ enum { PBG_CMD_SNP = 0, PBG_CMD_HAPLO = 1, PBG_CMD_DIVERGE = 2, PBG_CMD_TREE = 3
 enum { PBG_LD_RMIN = 4 };   /* pbg_cmd.output of PBG_CMD_LD: bit 2 */
 enum { PBG_HAPLO_NSL = 4 }; /* pbg_cmd.output of PBG_CMD_HAPLO: bit 2 */
 enum { PBG_HAPLO_XPNSL = 8 }; /* pbg_cmd.output of PBG_CMD_HAPLO: bit 3 */
+enum { PBG_NUCDIV_SNN = 1 };  /* pbg_cmd.output of PBG_CMD_NUCDIV: bit 0 = --snn, bits 1-16 PERMS, bits 17-30 SEED */
+#define PBG_NUCDIV_SNN_PERMS(output) (((output) >> 1) & 0xFFFF)
+#define PBG_NUCDIV_SNN_SEED(output)  (((output) >> 17) & 0x3FFF)
 
 typedef struct {
     int32_t  cmd;          /* PBG_CMD_*                                                   */
@@ -528,7 +584,16 @@ typedef struct {
                               "xpnsl[popI,popJ]:" one pos:mI:mJ:value:c per pooled site -- value the
                               unstandardised XP-nSL as %.5f or NA, c = cens[0] + cens[1] -- or NA when
                               there is none, after --nsl's columns; nothing with fewer than two
-                              populations; they ignore min_sites)                                 */
+                              populations; they ignore min_sites); nucdiv (which has no -o):
+                              PBG_NUCDIV_SNN = --snn, with PERMS in bits 1-16 and SEED in bits 17-30
+                              (PBG_NUCDIV_SNN_PERMS, PBG_NUCDIV_SNN_SEED), again no new field: with two
+                              or more populations a streamed run also runs pbg_window_snn on the
+                              command's windows with key0 = the contig position of row 0 -- the groups
+                              are all populations together (first, and only with three or more), then
+                              every pair i < j in lexicographic order -- and appends, per group,
+                              "snn[NAMES]:" and "psnn[NAMES]:" as %.5f, NAMES being popI,popJ or *,
+                              psnn = (ge + 1) / (PERMS + 1); both are NA for a window without a
+                              segregating site, psnn also when PERMS is 0; -k does not blank them   */
     int32_t  min_sites;    /* -k                                                          */
     int32_t  min_snps;     /* ld -n                                                       */
     int32_t  min_freq;     /* ld 1 / 2 (-e)                                               */
@@ -575,7 +640,8 @@ long pbg_take_text(pbg_ctx *ctx, char *out, size_t cap);
  * arrays and no D-statistic arrays either, so sfs output bits 1 (--joint) and 2 (--dstat) add
  * nothing here; no haplotype-spectrum arrays, so haplo's hfs adds nothing here; no Rmin arrays,
  * so ld's PBG_LD_RMIN adds nothing here; no nSL arrays, so haplo's PBG_HAPLO_NSL adds nothing here;
- * no XP-nSL arrays, so haplo's PBG_HAPLO_XPNSL adds nothing here. */
+ * no XP-nSL arrays, so haplo's PBG_HAPLO_XPNSL adds nothing here; no Snn arrays, so nucdiv's
+ * PBG_NUCDIV_SNN adds nothing here. */
 long pbg_format(const pbg_ctx *ctx, const pbg_cmd *cmd, const pbg_window_out *host_out, uint32_t n_win,
                 const int32_t *wbeg, const int32_t *wend, char *out, size_t cap, size_t *needed);
 

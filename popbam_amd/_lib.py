@@ -32,13 +32,17 @@ EXPORTS = ["pbg_create", "pbg_destroy", "pbg_last_error", "pbg_row_bytes", "pbg_
            "pbg_stream_rows", "pbg_stream_profile", "pbg_stream_error", "pbg_stream_close", "pbg_window_ld_decay",
            "pbg_jsfs_cells", "pbg_jsfs_pair_offset", "pbg_window_jsfs", "pbg_window_dstat",
            "pbg_hfs_stride", "pbg_window_hfs", "pbg_window_rmin", "pbg_window_nsl",
-           "pbg_window_xpnsl"]
+           "pbg_window_xpnsl", "pbg_window_snn", "pbg_snn_chunks"]
 
 PBG_DECAY_MAX_BINS = 256
 PBG_LD_RMIN = 4   # pbg_cmd.output of PBG_CMD_LD: --rmin
 PBG_HAPLO_NSL = 4   # pbg_cmd.output of PBG_CMD_HAPLO: --nsl
 PBG_HAPLO_XPNSL = 8   # pbg_cmd.output of PBG_CMD_HAPLO: --xpnsl
 PBG_DSTAT_MAX_TRIPLES = 4096
+PBG_NUCDIV_SNN = 1   # pbg_cmd.output of PBG_CMD_NUCDIV: --snn (bits 1-16 PERMS, bits 17-30 SEED)
+PBG_SNN_MAX_GROUPS = 4096
+PBG_SNN_MAX_PERMS = 65535
+PBG_SNN_MAX_SEED = 16383   # what the command line's 14 bits of pbg_cmd.output hold
 
 
 class PbgParams(C.Structure):
@@ -146,6 +150,15 @@ class PbgXpnslOut(C.Structure):
     _fields_ = [("n_var", C.c_void_p), ("row", C.c_void_p), ("m", C.c_void_p), ("sl", C.c_void_p), ("cens", C.c_void_p)]
 
 
+class PbgSnnOpts(C.Structure):
+    _fields_ = [("groups", C.POINTER(C.c_uint64)), ("n_groups", C.c_int32), ("n_perms", C.c_int32),   # a HOST array
+                ("seed", C.c_uint32), ("key0", C.c_uint32)]
+
+
+class PbgSnnOut(C.Structure):
+    _fields_ = [("diff", C.c_void_p), ("snn", C.c_void_p), ("near", C.c_void_p), ("ge", C.c_void_p)]
+
+
 class PbgStreamProf(C.Structure):
     _fields_ = [("h2d_bytes", C.c_uint64), ("pieces", C.c_uint32), ("chunks", C.c_uint32),
                 ("pinned_chunks", C.c_uint32), ("_pad", C.c_uint32), ("ms_stage", C.c_double),
@@ -217,6 +230,10 @@ def load(torch_first: bool = True):
     lib.pbg_window_nsl.restype = C.c_int
     lib.pbg_window_xpnsl.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgXpnslOpts), P(PbgXpnslOut), vp]
     lib.pbg_window_xpnsl.restype = C.c_int
+    lib.pbg_window_snn.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, P(PbgSnnOpts), P(PbgSnnOut), vp]
+    lib.pbg_window_snn.restype = C.c_int
+    lib.pbg_snn_chunks.argtypes = [C.c_uint32, C.c_int32, C.c_int32]
+    lib.pbg_snn_chunks.restype = C.c_int
     lib.pbg_build_info.argtypes = []
     lib.pbg_build_info.restype = C.c_char_p
     lib.pbg_check.argtypes = [vp, vp]

@@ -138,7 +138,7 @@ int event_time(pbg_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> pbg_ct
 
 namespace pbg {
 extern const int kBuildKind_call, kBuildKind_stats, kBuildKind_decay, kBuildKind_jsfs, kBuildKind_dstat, kBuildKind_hfs,
-    kBuildKind_rmin, kBuildKind_nsl, kBuildKind_xpnsl;
+    kBuildKind_rmin, kBuildKind_nsl, kBuildKind_xpnsl, kBuildKind_snn;
 }
 
 namespace {
@@ -388,10 +388,12 @@ void pbg_destroy(pbg_ctx *c) {
                     (void *)c->deep.blk_cnt, (void *)c->deep.raw, (void *)c->deep.pend,
                     (void *)c->d_decay_used, (void *)c->jsfs.d_pairs, (void *)c->jsfs.d_groups})
         if (p) (void)hipFree(p);
-    for (pbg::DevBuf *b : {&c->ws, &c->wsoff, &c->zns, &c->segcnt, &c->synth})
+    for (pbg::DevBuf *b : {&c->ws, &c->wsoff, &c->zns, &c->segcnt, &c->synth, &c->snn_diff})
         if (b->d) (void)hipFree(b->d);
     for (auto &t : c->tmpl) (void)hipFree(t.second);
     for (auto &l : c->dstat_lists)
+        if (l.d) (void)hipFree(l.d);
+    for (auto &l : c->snn_lists)
         if (l.d) (void)hipFree(l.d);
     for (auto *v : {&c->ev, &c->evc})
         for (auto &e : *v) {
@@ -522,7 +524,7 @@ int pbg_call_sites(pbg_ctx *c, const pbg_pileup *pl, void *rows, uint64_t *cb, v
 const char *pbg_build_info(void) {
     const int kind = std::max({(int)PBG_BUILD_KIND, pbg::kBuildKind_call, pbg::kBuildKind_stats, pbg::kBuildKind_decay,
                                pbg::kBuildKind_jsfs, pbg::kBuildKind_dstat, pbg::kBuildKind_hfs, pbg::kBuildKind_rmin,
-                               pbg::kBuildKind_nsl, pbg::kBuildKind_xpnsl});
+                               pbg::kBuildKind_nsl, pbg::kBuildKind_xpnsl, pbg::kBuildKind_snn});
     return kind == 2 ? "experiment" : kind == 1 ? "bounds" : "product";
 }
 
@@ -925,6 +927,87 @@ int pbg_window_xpnsl(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_wi
     A.sl = out->sl;
     A.cens = out->cens;
     HIPCHK(c, pbg::launch_window_xpnsl(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    return PBG_OK;
+}
+
+int pbg_snn_chunks(uint32_t n_win, int32_t n_groups, int32_t n_perms) { return pbg::snn_chunks(n_win, n_groups, n_perms); }
+
+int pbg_window_snn(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
+                   const pbg_snn_opts *o, const pbg_snn_out *out, void *stream) {
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    if (o->n_groups < 0 || o->n_groups > PBG_SNN_MAX_GROUPS)
+        return fail(c, PBG_E_ARG, "snn: n_groups must be in [0, " + std::to_string(PBG_SNN_MAX_GROUPS) + "]");
+    if (o->n_perms < 0 || o->n_perms > PBG_SNN_MAX_PERMS)
+        return fail(c, PBG_E_ARG, "snn: n_perms must be in [0, " + std::to_string(PBG_SNN_MAX_PERMS) + "]");
+    if (o->n_groups > 0 && !o->groups) return fail(c, PBG_E_ARG, "snn: null group list");
+    const int np = c->dp.npops, ng = o->n_groups;
+    std::vector<uint64_t> groups((size_t)ng);
+    for (int g = 0; g < ng; ++g) {
+        const uint64_t m = o->groups[g];
+        if (np < 64 && (m >> np) != 0)
+            return fail(c, PBG_E_ARG, "snn: group " + std::to_string(g) + " names a population outside 0.." + std::to_string(np - 1));
+        if (__builtin_popcountll(m) < 2)
+            return fail(c, PBG_E_ARG, "snn: group " + std::to_string(g) + " has fewer than two populations");
+        groups[(size_t)g] = m;
+    }
+    if (ng > 0)   // the members come from pop_mask, the labels' count from pop_n
+        if (int rc = check_pop_sizes(c, "snn")) return rc;
+    if (n_win == 0) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    const int n = c->dp.n;
+    const uint64_t npairs = (uint64_t)n * (uint64_t)(n - 1) / 2;
+    const bool stat = ng > 0 && (out->snn || out->near || out->ge);
+    if (!out->diff && !stat) return PBG_OK;   // nothing is wanted
+    const int chunks = out->ge ? pbg::snn_chunks(n_win, ng, o->n_perms) : 1;
+    if ((uint64_t)n_win * npairs > 0x7FFFFFFFull || (uint64_t)n_win * (uint64_t)std::max(ng, 1) * (uint64_t)chunks > 0x7FFFFFFFull)
+        return fail(c, PBG_E_ARG, "snn: too many windows");
+    HIPCHK(c, hipSetDevice(c->device));
+    pbg::SnnArgs A{};
+    A.wins = wins;
+    A.err = c->d_err;
+    A.n_pairs = (int32_t)npairs;
+    A.diff = out->diff;
+    if (!A.diff) {
+        if (int rc = pbg::grow(c, c->snn_diff, std::max<size_t>((size_t)n_win * (size_t)npairs * 4, 16))) return rc;
+        A.diff = (int32_t *)c->snn_diff.d;
+    }
+    if (stat) {
+        // the list's device copy, by content (pbg_ctx.h): written once, never overwritten
+        const uint64_t *d_groups = nullptr;
+        for (size_t k = c->snn_lists.size(); k-- > 0 && !d_groups;)
+            if (c->snn_lists[k].groups == groups) {
+                d_groups = c->snn_lists[k].d;
+                std::rotate(c->snn_lists.begin() + k, c->snn_lists.begin() + k + 1, c->snn_lists.end());
+            }
+        if (!d_groups) {
+            if (c->snn_lists.size() >= 16) {
+                HIPCHK(c, hipFree(c->snn_lists.front().d));   // waits for every launch that may read it
+                c->snn_lists.erase(c->snn_lists.begin());
+            }
+            uint64_t *d = nullptr;
+            HIPCHK(c, hipMalloc((void **)&d, groups.size() * 8));
+            const hipError_t e = hipMemcpy(d, groups.data(), groups.size() * 8, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(d);
+                HIPCHK(c, e);
+            }
+            c->snn_lists.push_back({std::move(groups), d});
+            d_groups = d;
+        }
+        A.groups = d_groups;
+        A.n_groups = ng;
+        A.n_perms = o->n_perms;
+        A.chunks = chunks;
+        A.per_chunk = (o->n_perms + chunks - 1) / chunks;
+        A.seed = o->seed;
+        A.key0 = o->key0;
+        A.snn = out->snn;
+        A.near = out->near;
+        A.ge = out->ge;
+        if (A.ge) HIPCHK(c, hipMemsetAsync(A.ge, 0, (size_t)n_win * (size_t)ng * 4, (hipStream_t)stream));
+    }
+    HIPCHK(c, pbg::launch_window_pairdiff(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    if (stat) HIPCHK(c, pbg::launch_window_snn(c->dp, n_win, A, (hipStream_t)stream));
     return PBG_OK;
 }
 

@@ -256,6 +256,26 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                     o.t("\tdxy[" + pn(c, i) + "-" + pn(c, j) + "]:\t");
                     if (ok) o.f(w.dxy[i * np + (j - (i + 1))]); else o.na();
                 }
+            // --snn: per group (all populations as "*" first, with three or more; then every pair) Hudson's
+            // Snn and its permutation p-value (ge + 1) / (PERMS + 1), after the reference's columns.  NA for
+            // a window without a segregating site, the p-value also with no permutations; -k does not
+            // blank them
+            if ((c.output & PBG_NUCDIV_SNN) && np > 1 && w.snn_val.size() == snn_groups(np).size() &&
+                w.snn_ge.size() == w.snn_val.size()) {
+                const int perms = PBG_NUCDIV_SNN_PERMS(c.output);
+                const bool seg = w.segsites >= 1;
+                size_t e = 0;
+                auto group = [&](const std::string &names) {
+                    o.t("\tsnn[" + names + "]:\t");
+                    if (seg) o.f(w.snn_val[e]); else o.na();
+                    o.t("\tpsnn[" + names + "]:\t");
+                    if (seg && perms > 0) o.f((double)(w.snn_ge[e] + 1) / (double)(perms + 1)); else o.na();
+                    ++e;
+                };
+                if (np >= 3) group("*");
+                for (int i = 0; i < np - 1; i++)
+                    for (int j = i + 1; j < np; j++) group(pn(c, i) + "," + pn(c, j));
+            }
             break;
         case PBG_CMD_SFS:  // print_sfs pop_sfs.cpp:293-317 (NA only for NaN)
             for (int i = 0; i < np; i++) {

@@ -436,6 +436,27 @@ struct XpnslArgs {
     int32_t *cens;             // [n_win * n_pairs * max_sites * 2] or null
 };
 
+// window_pairdiff_kernel and window_snn_kernel (pbg_window_snn): the exact difference matrix of a window
+// and Hudson's Snn with its permutation test per (window, group of populations).  The matrix is summed in
+// LDS (6 bytes a sample pair, dynamic); the Snn kernel's grid is (window, group, chunk of permutations),
+// the host choosing the chunks (snn_chunks) so that a few thousand workgroups exist even for few windows
+// and no chunk is too short to repay reading its group's part of the matrix.  No workspace.
+constexpr int kSnnWorkgroups = 4096;   // workgroups the chunking aims at
+constexpr int kSnnMinPerms = 16;       // permutations of a chunk, at least (but for the last)
+struct SnnArgs {
+    const pbg_window *wins;
+    int *err;
+    const uint64_t *groups;    // [n_groups] device copy: bit i = population i belongs
+    int32_t n_groups, n_perms;
+    int32_t chunks, per_chunk; // chunk k runs permutations [k * per_chunk, min(n_perms, (k + 1) * per_chunk))
+    uint32_t seed, key0;
+    int32_t n_pairs;           // n (n - 1) / 2
+    int32_t *diff;             // [n_win * n_pairs]: the caller's or the context's
+    double *snn;               // [n_win * n_groups] or null
+    int32_t *near;             // [n_win * n_groups * 2] or null
+    int32_t *ge;               // [n_win * n_groups] or null; zeroed by the call
+};
+
 // Samples deeper than the register sort width (16 reads) are finished outside the main call
 // kernel: it queues them as tasks (lane-per-task kernel), parks the position's other per-sample
 // info bytes in `info` ([n_sites * n], written only for such positions) and queues the
@@ -591,5 +612,10 @@ hipError_t launch_window_nsl(int row_bytes, const DevParams &P, const void *rows
 // xpnsl_kernel.hip (dynamic LDS: waves * nsl_wave_bytes(row_bytes, the largest pair table))
 hipError_t launch_window_xpnsl(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                                XpnslArgs A, hipStream_t stream);
+// snn_kernel.hip (pairdiff: dynamic LDS of 6 bytes a sample pair; snn: static LDS only)
+int snn_chunks(uint32_t n_win, int n_groups, int n_perms);
+hipError_t launch_window_pairdiff(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
+                                  const SnnArgs &A, hipStream_t stream);
+hipError_t launch_window_snn(const DevParams &P, uint32_t n_win, const SnnArgs &A, hipStream_t stream);
 
 }  // namespace pbg

@@ -54,6 +54,7 @@ struct StreamBufs {
     DevBuf rmin, rmin_cuts;              // ld --rmin: the counts and the intervals of one block of windows
     DevBuf nsl, nsl_sites;               // haplo --nsl: n_var, and row | m | cens | sl of one block of windows
     DevBuf xpnsl, xpnsl_sites;           // haplo --xpnsl: n_var, and sl | cens | m | row of one block of windows
+    DevBuf snn;                          // nucdiv --snn: snn | near | ge of one block of windows
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs
 };
@@ -120,6 +121,14 @@ struct pbg_ctx {
         uint32_t *d = nullptr;
     };
     std::vector<DstatList> dstat_lists;
+    // pbg_window_snn: device copies of the group lists seen so far, kept by content under the same rules;
+    // and the difference matrix of a call that asks for groups and gives no diff (it only grows)
+    struct SnnList {
+        std::vector<uint64_t> groups;
+        uint64_t *d = nullptr;
+    };
+    std::vector<SnnList> snn_lists;
+    pbg::DevBuf snn_diff;
     // samples deeper than the register sort width (call kernel): queues + parked info bytes
     pbg::DeepBufs deep{};
     size_t deep_sites_cap = 0, deep_info_cap = 0;

@@ -70,7 +70,22 @@ struct WindowHost {
     std::vector<int32_t> xp_n, xp_pos, xp_m, xp_cens, xp_pn;
     std::vector<int64_t> xp_sl;
     int xp_stride = 0;
+    // nucdiv --snn (PBG_NUCDIV_SNN in pbg_cmd.output): Snn of group e at snn_val[e] and its permutations
+    // with sum_r >= sum at snn_ge[e] (pbg_window_snn over snn_groups(np)); empty when the caller has none
+    // (pbg_format)
+    std::vector<double> snn_val;
+    std::vector<int32_t> snn_ge;
 };
+
+// nucdiv --snn's groups of n_pops populations: all of them together (first, and only with three or more),
+// then every pair i < j in lexicographic order; none for one population
+inline std::vector<uint64_t> snn_groups(int n_pops) {
+    std::vector<uint64_t> g;
+    if (n_pops >= 3) g.push_back(n_pops >= 64 ? ~0ULL : (1ULL << n_pops) - 1);
+    for (int i = 0; i < n_pops; ++i)
+        for (int j = i + 1; j < n_pops; ++j) g.push_back(1ULL << i | 1ULL << j);
+    return g;
+}
 
 // sfs --dstat's triples of n_pops populations: all (i, j, k) with i < j and k neither, in
 // lexicographic order -- n_pops * (n_pops - 1) / 2 * (n_pops - 2) of them

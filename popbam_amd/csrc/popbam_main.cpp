@@ -103,6 +103,7 @@ struct Options {
     int rmin = 0;                                                         // ld --rmin (0: off)
     int nsl = 0;                                                          // haplo --nsl (0: off)
     int xpnsl = 0;                                                        // haplo --xpnsl (0: off)
+    int snn = 0, snn_perms = 0, snn_seed = 0;                             // nucdiv --snn[=PERMS[,SEED]] (0: off)
     unsigned int win_size = 0;
     long double het_prior = 0.0001L;                                      // -z: parsed, unused
 };
@@ -322,6 +323,27 @@ Options parse_args(const std::string &cmd, const std::vector<std::string> &argv)
             if (o.output != 0) throw Fatal{"--decay needs -o 0"};
             o.decay_bin = (int)bin;
             o.decay_bins = (int)nb;
+        }
+    if (cmd == "nucdiv")   // extension: --snn[=PERMS[,SEED]] (one long token: never <in.bam> or <region>)
+        for (const std::string &a : argv) {
+            if (a != "--snn" && a.compare(0, 6, "--snn=") != 0) continue;
+            // PERMS in 0..PBG_SNN_MAX_PERMS and SEED in 0..16383, decimal digits only; bare --snn is 1000,0
+            std::string sp = "1000", ss = "0";
+            if (a != "--snn") {
+                const std::string v = a.substr(6);
+                const size_t comma = v.find(',');
+                sp = v.substr(0, comma);
+                if (comma != std::string::npos) ss = v.substr(comma + 1);
+            }
+            auto digits = [](const std::string &s) {
+                return !s.empty() && s.size() <= 10 && s.find_first_not_of("0123456789") == std::string::npos;
+            };
+            if (!digits(sp) || !digits(ss)) throw Fatal{"Not a valid snn option"};
+            const long long perms = std::stoll(sp), seed = std::stoll(ss);
+            if (perms > PBG_SNN_MAX_PERMS || seed > 16383) throw Fatal{"Not a valid snn option"};
+            o.snn = 1;
+            o.snn_perms = (int)perms;
+            o.snn_seed = (int)seed;
         }
     const std::vector<std::string> g = tk.globals();
     if (g.size() < 2) throw Fatal{"Need to specify BAM file name"};
@@ -763,7 +785,8 @@ std::string run(const std::string &cmd, const std::vector<std::string> &argv, in
         pbg_cmd c{};
         c.cmd = cmd_id(cmd);
         c.output = o.output | (cmd == "ld" && o.rmin ? PBG_LD_RMIN : 0) | (cmd == "haplo" && o.nsl ? PBG_HAPLO_NSL : 0) |
-                   (cmd == "haplo" && o.xpnsl ? PBG_HAPLO_XPNSL : 0);
+                   (cmd == "haplo" && o.xpnsl ? PBG_HAPLO_XPNSL : 0) |
+                   (cmd == "nucdiv" && o.snn ? PBG_NUCDIV_SNN | o.snn_perms << 1 | o.snn_seed << 17 : 0);
         c.min_sites = o.min_sites;
         c.min_snps = o.min_snps;
         c.min_freq = o.min_freq;

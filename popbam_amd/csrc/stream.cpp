@@ -165,7 +165,7 @@ int ensure_slot(pbg_ctx *c, pbg::StreamSlot &s, uint32_t chunk, size_t keys) {
     return PBG_OK;
 }
 
-// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin, haplo --nsl, haplo --xpnsl) is computed and copied
+// A command's extra table (sfs --joint, sfs --dstat, haplo --hfs, ld --rmin, haplo --nsl, haplo --xpnsl, nucdiv --snn) is computed and copied
 // to the host a block of windows at a time, so that its device buffer and its host copy stay at
 // kStage bytes each however many windows and populations there are.
 constexpr size_t kStage = 64u << 20;
@@ -577,6 +577,30 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
                   {h_xsl.data(), d_sl, slots * 16}};
         return pbg_window_xpnsl(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
     };
+    // nucdiv --snn: the difference-matrix and Snn kernels over the same windows and the command line's
+    // groups (its columns follow the reference's).  The matrix stays in the context's buffer.  key0 is the
+    // contig position of row 0, so a window's permutations depend on its first position alone
+    const std::vector<uint64_t> sgr = cmd->cmd == PBG_CMD_NUCDIV && (cmd->output & PBG_NUCDIV_SNN) ? pbg::snn_groups(np)
+                                                                                                  : std::vector<uint64_t>();
+    const size_t sG = sgr.size();
+    const bool snn = sG > 0;
+    WinBlocks sw = win_blocks(snn, nw, sG * 12 + (size_t)n * (n - 1) / 2 * 4);
+    std::vector<double> h_sval;
+    std::vector<int32_t> h_sge;
+    auto snn_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        const size_t per = (size_t)sw.size * sG, got = (size_t)cnt * sG;
+        const int src = grow(c, c->sb.snn, per * 12);
+        if (src) return src;
+        double *d_val = (double *)c->sb.snn.d;
+        int32_t *d_ge = (int32_t *)(d_val + per);
+        const pbg_snn_opts sopt{sgr.data(), (int32_t)sG, PBG_NUCDIV_SNN_PERMS(cmd->output),
+                                (uint32_t)PBG_NUCDIV_SNN_SEED(cmd->output), (uint32_t)dpos0};
+        const pbg_snn_out sout{nullptr, d_val, nullptr, d_ge};
+        h_sval.resize(got);
+        h_sge.resize(got);
+        copies = {{h_sval.data(), d_val, got * 8}, {h_sge.data(), d_ge, got * 4}};
+        return pbg_window_snn(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
+    };
     pbg::WindowHost wh;
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
@@ -637,6 +661,11 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             wh.xp_pn.assign(c->dp.pop_n, c->dp.pop_n + np);
             wh.xp_stride = (int)xS;
         }
+        if (snn) {
+            if (i >= sw.w1 && (rc = next_block(c, s, sw, i, nw, snn_call))) return rc;
+            wh.snn_val = slice(h_sval, (size_t)(i - sw.w0) * sG, sG);
+            wh.snn_ge = slice(h_sge, (size_t)(i - sw.w0) * sG, sG);
+        }
         wh.beg = win[i].first;
         wh.end = win[i].second;
         wh.num_sites = h_ns[i];
@@ -684,7 +713,7 @@ void pbg::stream_bufs_free(pbg_ctx *c) {
     pbg::StreamBufs &b = c->sb;
     for (auto &s : b.slot) free_slot(s);
     for (pbg::DevBuf *x : {&b.rows, &b.cb, &b.out, &b.decay, &b.jsfs, &b.dstat, &b.hfs, &b.rmin, &b.rmin_cuts, &b.nsl,
-                            &b.nsl_sites, &b.xpnsl, &b.xpnsl_sites})
+                            &b.nsl_sites, &b.xpnsl, &b.xpnsl_sites, &b.snn})
         if (x->d) (void)hipFree(x->d);
     for (auto &w : b.wins)
         if (w.d) (void)hipFree(w.d);

@@ -63,6 +63,8 @@ class _Cmd:
             c.output |= _lib.PBG_HAPLO_NSL
         if o.cmd == "haplo" and o.xpnsl:
             c.output |= _lib.PBG_HAPLO_XPNSL
+        if o.cmd == "nucdiv" and o.snn:
+            c.output |= _lib.PBG_NUCDIV_SNN | o.snn_perms << 1 | o.snn_seed << 17
         c.outidx = 0
         if o.flag & opt.BAM_OUTGROUP and o.cmd in ("sfs", "diverge", "snp"):   # nucdiv sets the flag, never reads -p
             idx = [i for i, s in enumerate(sm.samples) if s == o.outgroup]

@@ -32,6 +32,8 @@ CMD_IDS = {"snp": 0, "haplo": 1, "diverge": 2, "tree": 3, "nucdiv": 4, "ld": 5, 
 
 DECAY_MAX_BINS = 256   # PBG_DECAY_MAX_BINS (include/popbam_gpu.h)
 DSTAT_MAX_TRIPLES = 4096   # PBG_DSTAT_MAX_TRIPLES
+SNN_MAX_PERMS = 65535   # PBG_SNN_MAX_PERMS; bits 1-16 of pbg_cmd.output
+SNN_MAX_SEED = 16383    # bits 17-30 of pbg_cmd.output
 
 
 class PopbamError(RuntimeError):
@@ -65,6 +67,9 @@ class Options:
     rmin: int = 0          # ld --rmin: append Hudson and Kaplan's Rm and its intervals (0: off)
     nsl: int = 0           # haplo --nsl: append the per-site nSL of every population (0: off)
     xpnsl: int = 0         # haplo --xpnsl: append the per-site XP-nSL of every population pair (0: off)
+    snn: int = 0           # nucdiv --snn[=PERMS[,SEED]]: append Hudson's Snn and its permutation p-value (0: off)
+    snn_perms: int = 0
+    snn_seed: int = 0
     errors: list = field(default_factory=list)
 
 
@@ -237,6 +242,20 @@ def parse_args(cmd: str, argv: list[str]) -> Options:
             if o.output != 0:
                 raise PopbamError("--decay needs -o 0")
             o.decay_bin, o.decay_bins = int(m.group(1)), int(m.group(2))
+    if cmd == "nucdiv":   # extension: --snn[=PERMS[,SEED]] (one long token: never <in.bam> or <region>)
+        for a in argv:
+            if a != "--snn" and not a.startswith("--snn="):
+                continue
+            # PERMS in 0..SNN_MAX_PERMS and SEED in 0..SNN_MAX_SEED, decimal digits only; bare --snn is 1000,0
+            perms, seed = "1000", "0"
+            if a != "--snn":
+                m = re.fullmatch(r"([0-9]{1,10})(?:,([0-9]{1,10}))?", a[6:])
+                if not m:
+                    raise PopbamError("Not a valid snn option")
+                perms, seed = m.group(1), m.group(2) or "0"
+            if int(perms) > SNN_MAX_PERMS or int(seed) > SNN_MAX_SEED:
+                raise PopbamError("Not a valid snn option")
+            o.snn, o.snn_perms, o.snn_seed = 1, int(perms), int(seed)
     glob =[v for t, v in toks if t in ("G", "U", "N")]
     if len(glob) < 2:
         raise PopbamError("Need to specify BAM file name")

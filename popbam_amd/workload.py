@@ -408,6 +408,63 @@ class Xpnsl:
         return cls(hp.ctx, hp.n_win, max_sites, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
+class Snn:
+    """pbg_window_snn: the exact sample-by-sample difference matrix of every window and Hudson's Snn with
+    its permutation test per window and group of populations.  `groups` is a list of population-index
+    collections (a host array of the call; default_groups gives the command line's).  Owns the device
+    arrays -- diff[n_win, n (n - 1) / 2] (int32, pair (u, v), u < v, at u (2n - u - 1) / 2 + v - u - 1),
+    snn[n_win, n_groups] (float64), near[n_win, n_groups, 2] (int32: sum W, sum T) and ge[n_win, n_groups]
+    (int32: permutations with sum_r >= sum) -- and runs on a HotPath's rows and windows, or on any rows
+    tensor with a window list.  No groups is the difference matrix alone."""
+
+    NAMES = ("diff", "snn", "near", "ge")
+
+    def __init__(self, ctx: _lib.Context, n_win: int, groups=(), n_perms: int = 1000, seed: int = 0, key0: int = 0,
+                 device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        self.groups = [tuple(sorted(int(x) for x in g)) for g in groups]
+        self.n_groups = ng = len(self.groups)
+        self.n_perms = n_perms
+        n = ctx.params.n_samples
+        self.n_pairs = n * (n - 1) // 2
+        self._arr = (C.c_uint64 * max(1, ng))(*[sum(1 << i for i in g) for g in self.groups])
+        self.opts = _lib.PbgSnnOpts(C.cast(self._arr, C.POINTER(C.c_uint64)), ng, n_perms, seed, key0 & 0xFFFFFFFF)
+        self.diff = torch.zeros((n_win, self.n_pairs), dtype=torch.int32, device=device)
+        self.snn = torch.zeros((n_win, ng), dtype=torch.float64, device=device)
+        self.near = torch.zeros((n_win, ng, 2), dtype=torch.int32, device=device)
+        self.ge = torch.zeros((n_win, ng), dtype=torch.int32, device=device)
+        self.out = _lib.PbgSnnOut(_ptr(self.diff), *[_ptr(t) if ng > 0 else None for t in (self.snn, self.near, self.ge)])
+
+    @staticmethod
+    def default_groups(n_pops: int):
+        """The command line's groups: all populations together (with three or more), then every pair."""
+        allp = [tuple(range(n_pops))] if n_pops >= 3 else []
+        return allp + [(i, j) for i in range(n_pops) for j in range(i + 1, n_pops)]
+
+    @property
+    def chunks(self) -> int:
+        """The permutation chunks the call runs per (window, group)."""
+        return self.ctx.lib.pbg_snn_chunks(self.n_win, self.n_groups, self.n_perms)
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        return self.ctx.lib.pbg_window_snn(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
+                                           C.byref(self.opts), C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_snn")
+        return self
+
+    @classmethod
+    def of(cls, hp: "HotPath", groups=(), n_perms: int = 1000, seed: int = 0, key0: int = 0, stream=None) -> "Snn":
+        """The matrix and Snn of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, groups, n_perms, seed, key0, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites,
+                                                                                      stream)
+
+
 class HotPath:
     """call kernel (pileup -> rows) + window-statistics kernel (rows -> per-window stats)."""
 

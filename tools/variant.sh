@@ -22,6 +22,7 @@ $H $F --offload-arch=gfx950 -c -o $OUT/build/stats.o $C/stats_kernel.hip &
 [ -f $C/rmin_kernel.hip ] && { $H $F --offload-arch=gfx950 -c -o $OUT/build/rmin.o $C/rmin_kernel.hip & }
 [ -f $C/nsl_kernel.hip ] && { $H $F --offload-arch=gfx950 -c -o $OUT/build/nsl.o $C/nsl_kernel.hip & }
 [ -f $C/xpnsl_kernel.hip ] && { $H $F --offload-arch=gfx950 -c -o $OUT/build/xpnsl.o $C/xpnsl_kernel.hip & }
+[ -f $C/snn_kernel.hip ] && { $H $F --offload-arch=gfx950 -c -o $OUT/build/snn.o $C/snn_kernel.hip & }
 $H $F -x hip --offload-arch=gfx950 -c -o $OUT/build/api.o $C/api.cpp &
 $H $F -x hip --offload-arch=gfx950 -c -o $OUT/build/stream.o $C/stream.cpp &
 $H $F -c -o $OUT/build/tables.o $C/host_tables.cpp &

@@ -1,5 +1,5 @@
 """The window passes on one resident batch, for one or more built checkouts:
-`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin,nsl,xpnsl] [--tree DIR]... [--sites 50000000]
+`python tools/window_time.py [--passes sfs,decay,jsfs,dstat,hfs,rmin,nsl,xpnsl,snn] [--tree DIR]... [--sites 50000000]
 [--samples 12] [--pops 2] [--window 10000] [--depth 10] [--reps 25] [--seed 0xC0FFEE02] [--out FILE]`.
 
 The BASELINE configs[2] shape by default: 50 Msites x 12 samples x 2 populations, 10 kb reference
@@ -18,11 +18,15 @@ windows:
          outputs and max_sites = the largest count nsl_nvar found
   xpnsl  pbg_window_xpnsl count-only as xpnsl_nvar, and xpnsl, the full call with all five outputs and
          max_sites = the largest count xpnsl_nvar found.  Needs --pops 2 or more; skipped below that.
-A tree without one of the calls cannot run that pass; rmin, nsl and xpnsl alone are skipped there (and
+  snn    pbg_window_snn with n_groups = 0 and diff alone as pairdiff, and snn_1000: all populations together
+         (with three or more) and every pair, 1,000 permutations, all four outputs; its line also carries
+         snn_1000_ns_per_perm, the time per (window, group, permutation).  snn_1000 needs --pops 2 or more.
+A tree without one of the calls cannot run that pass; rmin, nsl, xpnsl and snn alone are skipped there (and
 named in `skipped`): rmin's yardstick is the decay_1x1 of the tree before it, nsl's is that tree's rmin,
 and with two trees of which the first has no nsl the comparison sets nsl_nvar against the first
 tree's rmin and gives nsl's ratio to it (when both trees have nsl, it is compared pass against pass
-like every other); xpnsl's yardsticks are the first tree's nsl_nvar and nsl, and the comparison gives the ratios.
+like every other); xpnsl's yardsticks are the first tree's nsl_nvar and nsl, and the comparison gives the ratios;
+pairdiff's yardstick is the first tree's sfs, which streams the same rows; snn_1000 has no predecessor.
 
 Every --tree (default: this checkout) is measured in a fresh child process that imports that tree's
 popbam_amd package and library; this process never touches the GPU.  Two or more trees are measured
@@ -41,7 +45,7 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin", "nsl", "xpnsl")
+PASSES = ("sfs", "decay", "jsfs", "dstat", "hfs", "rmin", "nsl", "xpnsl", "snn")
 SHAPE = ("samples", "pops", "sites", "window", "depth", "reps", "seed")
 
 
@@ -114,6 +118,16 @@ def child(a, passes):
         extra["xpnsl_sites"] = int(cnt.n_var.sum().item())
         if extra["xpnsl_max_sites"] > 0:
             runs["xpnsl"] = on_rows(workload.Xpnsl(ctx, hp.n_win, extra["xpnsl_max_sites"]))
+    if "snn" in passes and not hasattr(workload, "Snn"):
+        skipped.append("snn")   # a tree from before the call: its sfs is pairdiff's yardstick
+    elif "snn" in passes:
+        pd = workload.Snn(ctx, hp.n_win)
+        runs["pairdiff"] = on_rows(pd)
+        groups = workload.Snn.default_groups(a.pops)
+        if groups:
+            runs["snn_1000"] = on_rows(workload.Snn(ctx, hp.n_win, groups, 1000))
+            extra["snn_groups"] = len(groups)
+            extra["snn_chunks"] = workload.Snn(ctx, hp.n_win, groups, 1000).chunks
     for f in runs.values():   # warm: plans, workspace, tables, code objects
         f()
         f()
@@ -136,6 +150,8 @@ def child(a, passes):
         out[nm + "_ms_median"] = round(statistics.median(v), 4)
         out[nm + "_ms_min"] = round(min(v), 4)
         out[nm + "_ms_max"] = round(max(v), 4)
+    if "snn_1000" in ms:
+        out["snn_1000_ns_per_perm"] = round(statistics.median(ms["snn_1000"]) * 1e6 / (hp.n_win * extra["snn_groups"] * 1000), 3)
     print(json.dumps(out))
 
 
@@ -165,6 +181,13 @@ def compare(first, second):
             base = statistics.mean(r[yard + "_ms_median"] for r in first)
             new = statistics.mean(r[nm + "_ms_median"] for r in second)
             cmp[nm] = {f"first_{yard}_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
+    if "sfs_ms_median" in first[0] and "pairdiff_ms_median" in second[0]:   # pairdiff against the first tree's sfs
+        base = statistics.mean(r["sfs_ms_median"] for r in first)
+        new = statistics.mean(r["pairdiff_ms_median"] for r in second)
+        cmp["pairdiff"] = {"first_sfs_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
+    if "snn_1000_ms_median" in second[0]:
+        cmp["snn_1000"] = {"second_ms": round(statistics.mean(r["snn_1000_ms_median"] for r in second), 4),
+                           "ns_per_perm": round(statistics.mean(r["snn_1000_ns_per_perm"] for r in second), 3)}
     return cmp
 
 
