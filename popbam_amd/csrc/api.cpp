@@ -134,6 +134,34 @@ int event_time(pbg_ctx *c, std::vector<std::pair<hipEvent_t, hipEvent_t>> pbg_ct
     *launches = (uint32_t)c->ev_used;
     return PBG_OK;
 }
+
+// pbg_window_nsl and pbg_window_xpnsl: the shared checks (messages prefixed by `name`), then the launch.
+// A call whose chains need at least min_pops populations writes nothing below that.
+template <class Opts, class Out, class Launch>
+int window_tract(pbg_ctx *c, const char *name, int min_pops, const void *rows, uint32_t n_rows, const pbg_window *wins,
+                 uint32_t n_win, const Opts *o, const Out *out, void *stream, Launch launch) {
+    const std::string nm = name;
+    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
+    if (o->max_sites < 0) return fail(c, PBG_E_ARG, nm + ": max_sites must not be negative");
+    if ((out->row || out->m || out->sl || out->cens) && o->max_sites == 0)
+        return fail(c, PBG_E_ARG, nm + ": row, m, sl and cens need max_sites of at least 1");
+    if ((out->sl || out->cens) && !out->row) return fail(c, PBG_E_ARG, nm + ": sl and cens need row");
+    if (int rc = check_pop_sizes(c, name)) return rc;   // the pairs come from pop_n, the samples from pop_mask
+    if (n_win == 0 || c->dp.npops < min_pops) return PBG_OK;
+    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    pbg::TractArgs A{};
+    A.wins = wins;
+    A.err = c->d_err;
+    A.max_sites = o->max_sites;
+    A.n_var = out->n_var;
+    A.row = out->row;
+    A.m = out->m;
+    A.sl = out->sl;
+    A.cens = out->cens;
+    HIPCHK(c, launch(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
+    return PBG_OK;
+}
 }  // namespace
 
 namespace pbg {
@@ -884,50 +912,13 @@ int pbg_window_rmin(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_win
 
 int pbg_window_nsl(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
                    const pbg_nsl_opts *o, const pbg_nsl_out *out, void *stream) {
-    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
-    if (o->max_sites < 0) return fail(c, PBG_E_ARG, "nsl: max_sites must not be negative");
-    if ((out->row || out->m || out->sl || out->cens) && o->max_sites == 0)
-        return fail(c, PBG_E_ARG, "nsl: row, m, sl and cens need max_sites of at least 1");
-    if ((out->sl || out->cens) && !out->row) return fail(c, PBG_E_ARG, "nsl: sl and cens need row");
-    if (int rc = check_pop_sizes(c, "nsl")) return rc;   // the pairs come from pop_n, the samples from pop_mask
-    if (n_win == 0) return PBG_OK;
-    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    pbg::NslArgs A{};
-    A.wins = wins;
-    A.err = c->d_err;
-    A.max_sites = o->max_sites;
-    A.n_var = out->n_var;
-    A.row = out->row;
-    A.m = out->m;
-    A.sl = out->sl;
-    A.cens = out->cens;
-    HIPCHK(c, pbg::launch_window_nsl(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
-    return PBG_OK;
+    return window_tract(c, "nsl", 0, rows, n_rows, wins, n_win, o, out, stream, pbg::launch_window_nsl);
 }
 
+// one population has no pair: nothing is written
 int pbg_window_xpnsl(pbg_ctx *c, const void *rows, uint32_t n_rows, const pbg_window *wins, uint32_t n_win,
                      const pbg_xpnsl_opts *o, const pbg_xpnsl_out *out, void *stream) {
-    if (!c || !rows || !wins || !o || !out) return fail(c, PBG_E_ARG, "null argument");
-    if (o->max_sites < 0) return fail(c, PBG_E_ARG, "xpnsl: max_sites must not be negative");
-    if ((out->row || out->m || out->sl || out->cens) && o->max_sites == 0)
-        return fail(c, PBG_E_ARG, "xpnsl: row, m, sl and cens need max_sites of at least 1");
-    if ((out->sl || out->cens) && !out->row) return fail(c, PBG_E_ARG, "xpnsl: sl and cens need row");
-    if (int rc = check_pop_sizes(c, "xpnsl")) return rc;   // the pairs come from pop_n, the samples from pop_mask
-    if (n_win == 0 || c->dp.npops < 2) return PBG_OK;      // one population has no pair: nothing is written
-    if ((uintptr_t)rows & 15) return fail(c, PBG_E_ARG, "rows must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
-    pbg::XpnslArgs A{};
-    A.wins = wins;
-    A.err = c->d_err;
-    A.max_sites = o->max_sites;
-    A.n_var = out->n_var;
-    A.row = out->row;
-    A.m = out->m;
-    A.sl = out->sl;
-    A.cens = out->cens;
-    HIPCHK(c, pbg::launch_window_xpnsl(c->row_bytes, c->dp, rows, n_rows, n_win, A, (hipStream_t)stream));
-    return PBG_OK;
+    return window_tract(c, "xpnsl", 2, rows, n_rows, wins, n_win, o, out, stream, pbg::launch_window_xpnsl);
 }
 
 int pbg_snn_chunks(uint32_t n_win, int32_t n_groups, int32_t n_perms) { return pbg::snn_chunks(n_win, n_groups, n_perms); }

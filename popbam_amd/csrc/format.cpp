@@ -300,8 +300,8 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
                 }
             // --joint: per pair i < j Hudson's Fst and the joint spectrum's (n_i+1)*(n_j+1) cells
             // in cell order, after the reference's columns and --theta's
-            if ((c.output & 2) && np > 1 && w.jsfs_fst.size() == (size_t)np * (np - 1) / 2 && (int)w.jsfs_n.size() == np) {
-                const std::vector<int32_t> &pop_n = w.jsfs_n;
+            if ((c.output & 2) && np > 1 && w.jsfs_fst.size() == (size_t)np * (np - 1) / 2 && (int)w.pop_n.size() == np) {
+                const std::vector<int32_t> &pop_n = w.pop_n;
                 size_t p = 0, at = 0;
                 for (int i = 0; i < np - 1; i++)
                     for (int j = i + 1; j < np; j++, p++) {
@@ -473,24 +473,22 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
             // the derived count, the unstandardised nSL log((sl0 / P0) / (sl1 / P1)) (NA when a class
             // has no pair) and the number of tracts the window cut short -- after the reference's
             // columns and --hfs's (any -o); not subject to -k
-            if ((c.output & PBG_HAPLO_NSL) && (int)w.nsl_n.size() == np && (int)w.nsl_pn.size() == np &&
-                w.nsl_pos.size() == (size_t)np * w.nsl_stride && w.nsl_m.size() == w.nsl_pos.size() &&
-                w.nsl_sl.size() == 2 * w.nsl_pos.size() && w.nsl_cens.size() == 2 * w.nsl_pos.size())
+            if ((c.output & PBG_HAPLO_NSL) && (int)w.pop_n.size() == np && w.nsl.holds(np, 1))
                 for (int i = 0; i < np; i++) {
                     o.t("\tnsl[" + pn(c, i) + "]:\t");
-                    if (w.nsl_n[i] <= 0) o.t("NA");
-                    for (int k = 0; k < w.nsl_n[i] && k < w.nsl_stride; k++) {
-                        const size_t at = (size_t)i * w.nsl_stride + k;
-                        const long long m = w.nsl_m[at], z = w.nsl_pn[i] - m, p0 = z * (z - 1) / 2, p1 = m * (m - 1) / 2;
+                    if (w.nsl.n[i] <= 0) o.t("NA");
+                    for (int k = 0; k < w.nsl.n[i] && k < w.nsl.stride; k++) {
+                        const size_t at = (size_t)i * w.nsl.stride + k;
+                        const long long m = w.nsl.m[at], z = w.pop_n[i] - m, p0 = z * (z - 1) / 2, p1 = m * (m - 1) / 2;
                         if (k) o.t(",");
-                        o.i(w.nsl_pos[at] + 1);
+                        o.i(w.nsl.pos[at] + 1);
                         o.t(":");
                         o.i(m);
                         o.t(":");
                         if (p0 == 0 || p1 == 0) o.t("NA");
-                        else o.f(std::log(((double)w.nsl_sl[2 * at] / (double)p0) / ((double)w.nsl_sl[2 * at + 1] / (double)p1)));
+                        else o.f(std::log(((double)w.nsl.sl[2 * at] / (double)p0) / ((double)w.nsl.sl[2 * at + 1] / (double)p1)));
                         o.t(":");
-                        o.i((long long)w.nsl_cens[2 * at] + w.nsl_cens[2 * at + 1]);
+                        o.i((long long)w.nsl.cens[2 * at] + w.nsl.cens[2 * at + 1]);
                     }
                 }
             // --xpnsl: per population pair (i < j) the pooled sites as pos:mI:mJ:value:c -- the 1-based contig
@@ -498,29 +496,27 @@ void format_window(std::string &out, const pbg_cmd &c, int n, int np, uint32_t f
             // with C = n (n - 1) / 2 (NA when a side has no pair, or two samples that differ) and the number
             // of tracts the window cut short, both sides together -- after --nsl's columns; not subject to -k
             const size_t xp = (size_t)np * (np - 1) / 2;
-            if ((c.output & PBG_HAPLO_XPNSL) && xp > 0 && w.xp_n.size() == xp && (int)w.xp_pn.size() == np &&
-                w.xp_pos.size() == xp * w.xp_stride && w.xp_m.size() == 2 * w.xp_pos.size() &&
-                w.xp_sl.size() == 2 * w.xp_pos.size() && w.xp_cens.size() == 2 * w.xp_pos.size()) {
+            if ((c.output & PBG_HAPLO_XPNSL) && xp > 0 && (int)w.pop_n.size() == np && w.xpnsl.holds(xp, 2)) {
                 size_t p = 0;
                 for (int i = 0; i < np; i++)
                     for (int j = i + 1; j < np; j++, p++) {
                         o.t("\txpnsl[" + pn(c, i) + "," + pn(c, j) + "]:\t");
-                        if (w.xp_n[p] <= 0) o.t("NA");
-                        const long long c0 = (long long)w.xp_pn[i] * (w.xp_pn[i] - 1) / 2, c1 = (long long)w.xp_pn[j] * (w.xp_pn[j] - 1) / 2;
-                        for (int k = 0; k < w.xp_n[p] && k < w.xp_stride; k++) {
-                            const size_t at = p * w.xp_stride + k;
-                            const long long s0 = w.xp_sl[2 * at], s1 = w.xp_sl[2 * at + 1];
+                        if (w.xpnsl.n[p] <= 0) o.t("NA");
+                        const long long c0 = (long long)w.pop_n[i] * (w.pop_n[i] - 1) / 2, c1 = (long long)w.pop_n[j] * (w.pop_n[j] - 1) / 2;
+                        for (int k = 0; k < w.xpnsl.n[p] && k < w.xpnsl.stride; k++) {
+                            const size_t at = p * w.xpnsl.stride + k;
+                            const long long s0 = w.xpnsl.sl[2 * at], s1 = w.xpnsl.sl[2 * at + 1];
                             if (k) o.t(",");
-                            o.i(w.xp_pos[at] + 1);
+                            o.i(w.xpnsl.pos[at] + 1);
                             o.t(":");
-                            o.i(w.xp_m[2 * at]);
+                            o.i(w.xpnsl.m[2 * at]);
                             o.t(":");
-                            o.i(w.xp_m[2 * at + 1]);
+                            o.i(w.xpnsl.m[2 * at + 1]);
                             o.t(":");
                             if (c0 == 0 || c1 == 0 || s0 == 0 || s1 == 0) o.t("NA");
                             else o.f(std::log(((double)s0 / (double)c0) / ((double)s1 / (double)c1)));
                             o.t(":");
-                            o.i((long long)w.xp_cens[2 * at] + w.xp_cens[2 * at + 1]);
+                            o.i((long long)w.xpnsl.cens[2 * at] + w.xpnsl.cens[2 * at + 1]);
                         }
                     }
             }

@@ -402,38 +402,23 @@ struct RminArgs {
     int32_t *cuts;             // [n_win * npops * max_cuts * 2] or null
 };
 
-// window_nsl_kernel (pbg_window_nsl): the per-site nSL tract sums per (window, population).  One wave
-// per chain; a chain's row queue, one int32 per sample pair and the pair table live in LDS, so there is
-// no workspace.  The launcher sizes the per-wave LDS from the largest population and picks the waves
-// per workgroup (4, 2 or 1) that keep a launch within 64 KiB.
-struct NslArgs {
+// window_nsl_kernel (pbg_window_nsl) and window_xpnsl_kernel (pbg_window_xpnsl): the per-site tract sums
+// per chain -- a (window, population), or a (window, population pair) with both sides' sample pairs in
+// one table.  One wave per chain; a chain's row queue, one int32 per sample pair and the pair table live
+// in LDS (pbg_tract.h), so there is no workspace.  The launcher sizes the per-wave LDS from the largest
+// pair table and picks the waves per workgroup (4, 2 or 1) that keep a launch within 64 KiB.
+// m has two shapes: nSL's is one derived count per site, XP-nSL's one per side.
+struct TractArgs {
     const pbg_window *wins;
     int *err;
     int32_t max_sites;
-    int32_t pairs_max, waves;  // set by the launcher: n (n - 1) / 2 of the largest population; chains per workgroup
+    int32_t pairs_max, waves;  // set by the launcher: the largest pair table; chains per workgroup
     uint32_t wave_bytes;       // set by the launcher: LDS per wave
-    int32_t *n_var;            // [n_win * npops] or null
-    int32_t *row;              // [n_win * npops * max_sites] or null
-    int32_t *m;                // [n_win * npops * max_sites] or null
-    int64_t *sl;               // [n_win * npops * max_sites * 2] or null
-    int32_t *cens;             // [n_win * npops * max_sites * 2] or null
-};
-
-// window_xpnsl_kernel (pbg_window_xpnsl): the cross-population nSL tract sums per (window, population
-// pair).  One wave per chain and nsl's per-wave LDS layout, with both sides' sample pairs in one table:
-// the launcher sizes it from the largest C(n_i, 2) + C(n_j, 2) over the pairs and picks the waves per
-// workgroup (4, 2 or 1) that keep a launch within 64 KiB.  No workspace.
-struct XpnslArgs {
-    const pbg_window *wins;
-    int *err;
-    int32_t max_sites;
-    int32_t pairs_max, waves;  // set by the launcher: the largest table; chains per workgroup
-    uint32_t wave_bytes;       // set by the launcher: LDS per wave
-    int32_t *n_var;            // [n_win * n_pairs] or null
-    int32_t *row;              // [n_win * n_pairs * max_sites] or null
-    int32_t *m;                // [n_win * n_pairs * max_sites * 2] or null
-    int64_t *sl;               // [n_win * n_pairs * max_sites * 2] or null
-    int32_t *cens;             // [n_win * n_pairs * max_sites * 2] or null
+    int32_t *n_var;            // [chains] or null
+    int32_t *row;              // [chains * max_sites] or null
+    int32_t *m;                // nSL [chains * max_sites], XP-nSL [chains * max_sites * 2], or null
+    int64_t *sl;               // [chains * max_sites * 2] or null
+    int32_t *cens;             // [chains * max_sites * 2] or null
 };
 
 // window_pairdiff_kernel and window_snn_kernel (pbg_window_snn): the exact difference matrix of a window
@@ -605,13 +590,11 @@ hipError_t launch_window_hfs(int row_bytes, const DevParams &P, const void *rows
 // rmin_kernel.hip (static LDS only)
 hipError_t launch_window_rmin(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
                               const RminArgs &A, hipStream_t stream);
-// nsl_kernel.hip (dynamic LDS: waves * nsl_wave_bytes(row_bytes, pairs of the largest population))
-size_t nsl_wave_bytes(int row_bytes, int pairs_max);
+// nsl_kernel.hip and xpnsl_kernel.hip (dynamic LDS: pbg_tract.h's plan for the launch's largest pair table)
 hipError_t launch_window_nsl(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
-                             NslArgs A, hipStream_t stream);
-// xpnsl_kernel.hip (dynamic LDS: waves * nsl_wave_bytes(row_bytes, the largest pair table))
+                             TractArgs A, hipStream_t stream);
 hipError_t launch_window_xpnsl(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,
-                               XpnslArgs A, hipStream_t stream);
+                               TractArgs A, hipStream_t stream);
 // snn_kernel.hip (pairdiff: dynamic LDS of 6 bytes a sample pair; snn: static LDS only)
 int snn_chunks(uint32_t n_win, int n_groups, int n_perms);
 hipError_t launch_window_pairdiff(int row_bytes, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win,

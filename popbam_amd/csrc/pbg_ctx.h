@@ -52,8 +52,8 @@ struct StreamBufs {
     DevBuf dstat;                        // sfs --dstat: sums | d | fd | fdm of one block of windows
     DevBuf hfs;                          // haplo --hfs: h | counts | k of one block of windows
     DevBuf rmin, rmin_cuts;              // ld --rmin: the counts and the intervals of one block of windows
-    DevBuf nsl, nsl_sites;               // haplo --nsl: n_var, and row | m | cens | sl of one block of windows
-    DevBuf xpnsl, xpnsl_sites;           // haplo --xpnsl: n_var, and sl | cens | m | row of one block of windows
+    DevBuf nsl, nsl_sites;               // haplo --nsl: n_var, and sl | cens | m | row of one block of windows
+    DevBuf xpnsl, xpnsl_sites;           // haplo --xpnsl: the same per population pair
     DevBuf snn;                          // nucdiv --snn: snn | near | ge of one block of windows
     std::vector<WinList> wins;          // most recent last
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // profiling pairs

@@ -21,6 +21,32 @@ void build_sfs_constants(int n, std::vector<double> &a1, std::vector<double> &a2
                          std::vector<double> &e2);
 void build_r2_table(int n_pop, std::vector<double> &t);
 
+// The per-site tract table of a window (pbg_window_nsl, pbg_window_xpnsl): chain p has n[p] sites; site k
+// at s = p * stride + k: pos[s] its contig position, 0-based, m[m_per * s ..] the derived counts,
+// sl[2 * s ..] and cens[2 * s ..] the call's sums.  Empty when the caller has none (pbg_format).
+struct TractTable {
+    std::vector<int32_t> n, pos, m, cens;
+    std::vector<int64_t> sl;
+    int stride = 0;
+    // whether it holds `chains` chains with m_per ints of m a site
+    bool holds(size_t chains, size_t m_per) const {
+        return n.size() == chains && pos.size() == chains * stride && m.size() == m_per * pos.size() &&
+               sl.size() == 2 * pos.size() && cens.size() == 2 * pos.size();
+    }
+    // block-wide arrays of blk_stride slots a chain -> the `chains` chains from chain e0 on, rows -> positions
+    void slice(const TractTable &blk, size_t e0, size_t chains, size_t m_per, int32_t pos0) {
+        const size_t s0 = e0 * blk.stride, per = chains * blk.stride;
+        stride = blk.stride;
+        n.assign(blk.n.begin() + e0, blk.n.begin() + e0 + chains);
+        pos.assign(blk.pos.begin() + s0, blk.pos.begin() + s0 + per);
+        for (int32_t &x : pos)
+            if (x >= 0) x += pos0;   // row -> contig position
+        m.assign(blk.m.begin() + s0 * m_per, blk.m.begin() + (s0 + per) * m_per);
+        cens.assign(blk.cens.begin() + s0 * 2, blk.cens.begin() + (s0 + per) * 2);
+        sl.assign(blk.sl.begin() + s0 * 2, blk.sl.begin() + (s0 + per) * 2);
+    }
+};
+
 // Host copies of one window's results, as print_<stat> needs them.
 struct WindowHost {
     int32_t beg = 0, end = 0;       // contig coordinates [beg, end)
@@ -37,10 +63,9 @@ struct WindowHost {
     std::vector<int64_t> decay_pairs;
     std::vector<double> decay_sum;
     // sfs --joint (pbg_cmd.output bit 1): Fst of pair p at [p], the window's packed cells
-    // (pbg_window_jsfs) and the population sizes that shape them; empty when the caller has none
-    // (pbg_format)
+    // (pbg_window_jsfs), shaped by pop_n; empty when the caller has none (pbg_format)
     std::vector<double> jsfs_fst;
-    std::vector<int32_t> jsfs_cells, jsfs_n;
+    std::vector<int32_t> jsfs_cells;
     // sfs --dstat (pbg_cmd.output bit 2): D, f_d, f_dM of triple t at [t] and its six sums at
     // [t * 6] (pbg_window_dstat over dstat_triples(np)); empty when the caller has none (pbg_format)
     std::vector<double> dstat_d, dstat_fd, dstat_fdm;
@@ -56,20 +81,11 @@ struct WindowHost {
     // (pbg_window_rmin); empty when the caller has none (pbg_format)
     std::vector<int32_t> rmin_n, rmin_cuts;
     int rmin_stride = 0;
-    // haplo --nsl (PBG_HAPLO_NSL in pbg_cmd.output): population p has nsl_n[p] variable sites; site k at
-    // s = p * nsl_stride + k: nsl_pos[s] its contig position, 0-based, nsl_m[s] the derived count,
-    // nsl_sl[2 * s + c] and nsl_cens[2 * s + side] the sums of pbg_window_nsl; nsl_pn[p] the
-    // population's size; empty when the caller has none (pbg_format)
-    std::vector<int32_t> nsl_n, nsl_pos, nsl_m, nsl_cens, nsl_pn;
-    std::vector<int64_t> nsl_sl;
-    int nsl_stride = 0;
-    // haplo --xpnsl (PBG_HAPLO_XPNSL in pbg_cmd.output): population pair p (i < j, lexicographic) has
-    // xp_n[p] pooled sites; site k at s = p * xp_stride + k: xp_pos[s] its contig position, 0-based,
-    // xp_m[2 * s + side], xp_sl[2 * s + side] and xp_cens[2 * s + side] the numbers of pbg_window_xpnsl;
-    // xp_pn[i] population i's size; empty when the caller has none (pbg_format)
-    std::vector<int32_t> xp_n, xp_pos, xp_m, xp_cens, xp_pn;
-    std::vector<int64_t> xp_sl;
-    int xp_stride = 0;
+    // haplo --nsl and --xpnsl (PBG_HAPLO_NSL, PBG_HAPLO_XPNSL in pbg_cmd.output): the chains are the
+    // populations, and the population pairs (i < j, lexicographic), with two ints of m a site
+    TractTable nsl, xpnsl;
+    // the populations' sizes, for --joint, --nsl and --xpnsl; empty when the caller has none (pbg_format)
+    std::vector<int32_t> pop_n;
     // nucdiv --snn (PBG_NUCDIV_SNN in pbg_cmd.output): Snn of group e at snn_val[e] and its permutations
     // with sum_r >= sum at snn_ge[e] (pbg_window_snn over snn_groups(np)); empty when the caller has none
     // (pbg_format)

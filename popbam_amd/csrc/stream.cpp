@@ -199,6 +199,36 @@ int next_block(pbg_ctx *c, hipStream_t s, WinBlocks &b, uint32_t first, uint32_t
     return PBG_OK;
 }
 
+// A block's per-site tract table (haplo --nsl, --xpnsl) for next_block: `chains` chains a window, m_per
+// ints of m a slot.  The per-site arrays need a stride, so call(max_sites, n_var, row, m, sl, cens), which
+// runs the entry point over the block's cnt windows, runs twice: once for the counts alone, then, when
+// some count is not 0, again with max_sites = the block's largest count, which becomes blk.stride.
+template <class Call>
+int stage_tract(pbg_ctx *c, hipStream_t s, pbg::DevBuf &counts, pbg::DevBuf &sites, uint32_t block_windows, uint32_t cnt,
+                size_t chains, size_t m_per, pbg::TractTable &blk, std::vector<D2H> &copies, Call call) {
+    const size_t got = (size_t)cnt * chains;
+    int rc = grow(c, counts, ((size_t)block_windows * chains * 4 + 255) & ~(size_t)255);
+    if (rc) return rc;
+    int32_t *d_n = (int32_t *)counts.d;
+    if ((rc = call(0, d_n, nullptr, nullptr, nullptr, nullptr))) return rc;
+    blk.n.resize(got);
+    HIPCHK(c, hipMemcpyAsync(blk.n.data(), d_n, got * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    blk.stride = std::max(0, *std::max_element(blk.n.begin(), blk.n.end()));
+    const size_t slots = got * blk.stride;
+    blk.pos.resize(slots);
+    blk.m.resize(slots * m_per);
+    blk.cens.resize(slots * 2);
+    blk.sl.resize(slots * 2);
+    if (slots == 0) return PBG_OK;
+    if ((rc = grow(c, sites, slots * (16 + 8 + 4 * m_per + 4)))) return rc;
+    int64_t *d_sl = (int64_t *)sites.d;   // the widest first: every part stays aligned
+    int32_t *d_cens = (int32_t *)(d_sl + slots * 2), *d_m = d_cens + slots * 2, *d_row = d_m + slots * m_per;
+    copies = {{blk.pos.data(), d_row, slots * 4}, {blk.m.data(), d_m, slots * m_per * 4}, {blk.cens.data(), d_cens, slots * 8},
+              {blk.sl.data(), d_sl, slots * 16}};
+    return call(blk.stride, nullptr, d_row, d_m, d_sl, d_cens);
+}
+
 // a pair of timing events from the context's pool
 int ev_pair(pbg_stream *st, int kind, hipEvent_t &a, hipEvent_t &b) {
     pbg_ctx *c = st->c;
@@ -504,78 +534,32 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         copies = {{h_rcuts.data(), cuts_out.cuts, got * rS * 8}};
         return pbg_window_rmin(c, d_rows, dsites, d_win + first, cnt, &copt, &cuts_out, s);
     };
-    // haplo --nsl: the nSL kernel over the same windows (its columns follow the reference's and
-    // --hfs's).  The per-site arrays need a stride, so a block is run twice as for --rmin: once for
-    // the counts alone, then, when some count is not 0, again with max_sites = the block's largest
-    // count.  A block is sized as if that were kNslGuess; a larger one only makes the block's
-    // per-site buffer larger.
-    const bool nsl = cmd->cmd == PBG_CMD_HAPLO && (cmd->output & PBG_HAPLO_NSL);
-    constexpr size_t kNslGuess = 256, kNslSite = 4 + 4 + 8 + 16;   // row, m, cens, sl: bytes per slot
-    WinBlocks nb = win_blocks(nsl, nw, (size_t)np * (4 + kNslSite * kNslGuess));
-    std::vector<int32_t> h_nn, h_nrow, h_nm, h_ncens;
-    std::vector<int64_t> h_nsl;
-    size_t nS = 0;   // the block's stride: slots per (window, population)
-    auto nsl_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
-        const size_t got = (size_t)cnt * np;
-        int nrc = grow(c, c->sb.nsl, al((size_t)nb.size * np * 4));
-        if (nrc) return nrc;
-        const pbg_nsl_opts nopt{0, 0};
-        const pbg_nsl_out nout{(int32_t *)c->sb.nsl.d, nullptr, nullptr, nullptr, nullptr};
-        if ((nrc = pbg_window_nsl(c, d_rows, dsites, d_win + first, cnt, &nopt, &nout, s))) return nrc;
-        h_nn.resize(got);
-        HIPCHK(c, d2h(h_nn.data(), nout.n_var, got * 4));
-        HIPCHK(c, hipStreamSynchronize(s));
-        nS = (size_t)std::max(0, *std::max_element(h_nn.begin(), h_nn.end()));
-        const size_t slots = got * nS;
-        h_nrow.resize(slots);
-        h_nm.resize(slots);
-        h_ncens.resize(slots * 2);
-        h_nsl.resize(slots * 2);
-        if (nS == 0) return PBG_OK;
-        if ((nrc = grow(c, c->sb.nsl_sites, slots * kNslSite))) return nrc;
-        int64_t *d_sl = (int64_t *)c->sb.nsl_sites.d;   // the widest first: every part stays aligned
-        int32_t *d_cens = (int32_t *)(d_sl + slots * 2), *d_row = d_cens + slots * 2, *d_m = d_row + slots;
-        const pbg_nsl_opts sopt{(int32_t)nS, 0};
-        const pbg_nsl_out sout{nullptr, d_row, d_m, d_sl, d_cens};
-        copies = {{h_nrow.data(), d_row, slots * 4}, {h_nm.data(), d_m, slots * 4}, {h_ncens.data(), d_cens, slots * 8},
-                  {h_nsl.data(), d_sl, slots * 16}};
-        return pbg_window_nsl(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
-    };
-    // haplo --xpnsl: the XP-nSL kernel over the same windows, per population pair (its columns follow
-    // --nsl's), staged as --nsl is: a block runs once for the counts alone, then, when some count is not
-    // 0, again with max_sites = the block's largest count.  Fewer than two populations: no pair, no call.
+    // haplo --nsl and --xpnsl: the tract kernels over the same windows, per population and per population
+    // pair (their columns follow the reference's, --hfs's, and --nsl's), staged by stage_tract.  A block is
+    // sized as if its stride were kNslGuess; a larger one only makes the block's per-site buffer larger.
+    // Fewer than two populations: no pair, no call.
     const size_t xP = (size_t)np * (np - 1) / 2;
+    const bool nsl = cmd->cmd == PBG_CMD_HAPLO && (cmd->output & PBG_HAPLO_NSL);
     const bool xpnsl = cmd->cmd == PBG_CMD_HAPLO && (cmd->output & PBG_HAPLO_XPNSL) && xP > 0;
-    constexpr size_t kXpSite = 16 + 8 + 8 + 4;   // sl, cens, m, row: bytes per slot
-    WinBlocks xb = win_blocks(xpnsl, nw, xP * (4 + kXpSite * kNslGuess));
-    std::vector<int32_t> h_xn, h_xrow, h_xm, h_xcens;
-    std::vector<int64_t> h_xsl;
-    size_t xS = 0;   // the block's stride: slots per (window, pair)
+    constexpr size_t kNslGuess = 256;   // a slot is 32 bytes of sl, cens, m and row, 36 with XP-nSL's two m
+    WinBlocks nb = win_blocks(nsl, nw, (size_t)np * (4 + 32 * kNslGuess));
+    WinBlocks xb = win_blocks(xpnsl, nw, xP * (4 + 36 * kNslGuess));
+    pbg::TractTable h_nsl, h_xp;   // a block's tables, pos still the row
+    auto nsl_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
+        return stage_tract(c, s, c->sb.nsl, c->sb.nsl_sites, nb.size, cnt, np, 1, h_nsl, copies,
+                           [&](int ms, int32_t *n_var, int32_t *row, int32_t *m, int64_t *sl, int32_t *cens) {
+                               const pbg_nsl_opts o{ms, 0};
+                               const pbg_nsl_out out{n_var, row, m, sl, cens};
+                               return pbg_window_nsl(c, d_rows, dsites, d_win + first, cnt, &o, &out, s);
+                           });
+    };
     auto xpnsl_call = [&](uint32_t first, uint32_t cnt, std::vector<D2H> &copies) -> int {
-        const size_t got = (size_t)cnt * xP;
-        int xrc = grow(c, c->sb.xpnsl, al((size_t)xb.size * xP * 4));
-        if (xrc) return xrc;
-        const pbg_xpnsl_opts nopt{0, 0};
-        const pbg_xpnsl_out nout{(int32_t *)c->sb.xpnsl.d, nullptr, nullptr, nullptr, nullptr};
-        if ((xrc = pbg_window_xpnsl(c, d_rows, dsites, d_win + first, cnt, &nopt, &nout, s))) return xrc;
-        h_xn.resize(got);
-        HIPCHK(c, d2h(h_xn.data(), nout.n_var, got * 4));
-        HIPCHK(c, hipStreamSynchronize(s));
-        xS = (size_t)std::max(0, *std::max_element(h_xn.begin(), h_xn.end()));
-        const size_t slots = got * xS;
-        h_xrow.resize(slots);
-        h_xm.resize(slots * 2);
-        h_xcens.resize(slots * 2);
-        h_xsl.resize(slots * 2);
-        if (xS == 0) return PBG_OK;
-        if ((xrc = grow(c, c->sb.xpnsl_sites, slots * kXpSite))) return xrc;
-        int64_t *d_sl = (int64_t *)c->sb.xpnsl_sites.d;   // the widest first: every part stays aligned
-        int32_t *d_cens = (int32_t *)(d_sl + slots * 2), *d_m = d_cens + slots * 2, *d_row = d_m + slots * 2;
-        const pbg_xpnsl_opts sopt{(int32_t)xS, 0};
-        const pbg_xpnsl_out sout{nullptr, d_row, d_m, d_sl, d_cens};
-        copies = {{h_xrow.data(), d_row, slots * 4}, {h_xm.data(), d_m, slots * 8}, {h_xcens.data(), d_cens, slots * 8},
-                  {h_xsl.data(), d_sl, slots * 16}};
-        return pbg_window_xpnsl(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
+        return stage_tract(c, s, c->sb.xpnsl, c->sb.xpnsl_sites, xb.size, cnt, xP, 2, h_xp, copies,
+                           [&](int ms, int32_t *n_var, int32_t *row, int32_t *m, int64_t *sl, int32_t *cens) {
+                               const pbg_xpnsl_opts o{ms, 0};
+                               const pbg_xpnsl_out out{n_var, row, m, sl, cens};
+                               return pbg_window_xpnsl(c, d_rows, dsites, d_win + first, cnt, &o, &out, s);
+                           });
     };
     // nucdiv --snn: the difference-matrix and Snn kernels over the same windows and the command line's
     // groups (its columns follow the reference's).  The matrix stays in the context's buffer.  key0 is the
@@ -602,6 +586,7 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         return pbg_window_snn(c, d_rows, dsites, d_win + first, cnt, &sopt, &sout, s);
     };
     pbg::WindowHost wh;
+    wh.pop_n.assign(c->dp.pop_n, c->dp.pop_n + np);
     auto slice =[](const auto &v, size_t off, size_t cnt) {
         using T = typename std::decay_t<decltype(v)>::value_type;
         return std::vector<T>(v.begin() + off, v.begin() + off + cnt);
@@ -611,7 +596,6 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
             if (i >= jw.w1 && (rc = next_block(c, s, jw, i, nw, joint_call))) return rc;
             wh.jsfs_fst = slice(h_jfst, (size_t)(i - jw.w0) * jP, jP);
             wh.jsfs_cells = slice(h_jcells, (size_t)(i - jw.w0) * jC, jC);
-            wh.jsfs_n.assign(c->dp.pop_n, c->dp.pop_n + np);
         }
         if (dstat) {
             if (i >= dw.w1 && (rc = next_block(c, s, dw, i, nw, dstat_call))) return rc;
@@ -637,29 +621,11 @@ int format_command(pbg_ctx *c, const pbg_cmd *cmd, const void *d_rows, uint32_t 
         }
         if (nsl) {
             if (i >= nb.w1 && (rc = next_block(c, s, nb, i, nw, nsl_call))) return rc;
-            const size_t e0 = (size_t)(i - nb.w0) * np, per = (size_t)np * nS;
-            wh.nsl_n = slice(h_nn, e0, np);
-            wh.nsl_pos = slice(h_nrow, e0 * nS, per);
-            for (int32_t &x : wh.nsl_pos)
-                if (x >= 0) x += (int32_t)dpos0;   // row -> contig position
-            wh.nsl_m = slice(h_nm, e0 * nS, per);
-            wh.nsl_cens = slice(h_ncens, e0 * nS * 2, per * 2);
-            wh.nsl_sl = slice(h_nsl, e0 * nS * 2, per * 2);
-            wh.nsl_pn.assign(c->dp.pop_n, c->dp.pop_n + np);
-            wh.nsl_stride = (int)nS;
+            wh.nsl.slice(h_nsl, (size_t)(i - nb.w0) * np, np, 1, (int32_t)dpos0);
         }
         if (xpnsl) {
             if (i >= xb.w1 && (rc = next_block(c, s, xb, i, nw, xpnsl_call))) return rc;
-            const size_t e0 = (size_t)(i - xb.w0) * xP, per = xP * xS;
-            wh.xp_n = slice(h_xn, e0, xP);
-            wh.xp_pos = slice(h_xrow, e0 * xS, per);
-            for (int32_t &x : wh.xp_pos)
-                if (x >= 0) x += (int32_t)dpos0;   // row -> contig position
-            wh.xp_m = slice(h_xm, e0 * xS * 2, per * 2);
-            wh.xp_cens = slice(h_xcens, e0 * xS * 2, per * 2);
-            wh.xp_sl = slice(h_xsl, e0 * xS * 2, per * 2);
-            wh.xp_pn.assign(c->dp.pop_n, c->dp.pop_n + np);
-            wh.xp_stride = (int)xS;
+            wh.xpnsl.slice(h_xp, (size_t)(i - xb.w0) * xP, xP, 2, (int32_t)dpos0);
         }
         if (snn) {
             if (i >= sw.w1 && (rc = next_block(c, s, sw, i, nw, snn_call))) return rc;

@@ -9,11 +9,10 @@
 // ... and k, k + 1, ... over the pooled list, its tract length is L = l + r - 1, and sl[k][s] is the sum
 // of L over side s's agreeing pairs.
 //
-// The structure is nsl_kernel.hip's: one wave per chain, `waves` chains per workgroup (4, 2 or 1 by the
-// LDS plan), nothing shared between the waves, no workgroup barrier; the passes count, forward and
-// backward; one last[p] per sample pair, both sides' pairs in one table (side 0's, then side 1's).
-// Forward, last[p] is the last site at which pair p differed (-1 before the first); backward it is the
-// mirror image from V.  Every agreeing pair is counted by both walks, so
+// The walk itself -- one wave per chain, the passes count, forward and backward, one last[p] per sample
+// pair, the LDS and the launch plan -- is pbg_tract.h's; both sides' pairs share the table (side 0's,
+// then side 1's).  Forward, last[p] is the last site at which pair p differed (-1 before the first);
+// backward it is the mirror image from V.  Every agreeing pair is counted by both walks, so
 // sl[k][s] = left + right - A_s with A_s = C(m_s, 2) + C(n_s - m_s, 2), the agreeing pairs at the site.
 //
 // There are no classes, so a side's sum over its agreeing pairs is its sum over all pairs less that over
@@ -31,11 +30,9 @@
 // bound of the split scan (wave_sum38), and |sumlast_s| <= 7,875 * 2^31 < 2^44.  Two runs give the
 // same bytes.
 //
-// The backward walk reads the sites back through row[] after a device-scope fence (which is why sl and
-// cens need row), 64 at a time from the back, the next trip's loads issued before this trip's walk; a
-// row index is checked against n_rows before the row is read.
 #include "pbg_common.h"
 #include "pbg_rows.h"
+#include "pbg_tract.h"
 
 namespace pbg {
 extern const int kBuildKind_xpnsl = PBG_BUILD_KIND;   // pbg_build_info()
@@ -45,159 +42,49 @@ namespace pbg {
 
 namespace {
 
-// the sum of v < 2^38 over the wave, wave-uniform: two integer scans of 20- and 18-bit halves
-__device__ __forceinline__ uint64_t wave_sum38(uint64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_s((uint32_t)v & 0xFFFFFu), 63);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_s((uint32_t)(v >> 20)), 63);
-    return ((uint64_t)hi << 20) + lo;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_s(v), 63);
-}
-
 __device__ __forceinline__ uint64_t join(uint64_t a, uint64_t b) { return a | b; }
 __device__ __forceinline__ M2 join(M2 a, M2 b) { return {a.lo | b.lo, a.hi | b.hi}; }
 
-// the number of set bits of pm below bit l
-__device__ __forceinline__ int rank_below(uint64_t pm, int l) { return (int)pc(pm & ((1ULL << l) - 1)); }
-__device__ __forceinline__ int rank_below(M2 pm, int l) {
-    return l < 64 ? rank_below(pm.lo, l) : (int)pc(pm.lo) + rank_below(pm.hi, l - 64);
-}
-
-// row ri (< n_rows) alone: its sample bits
 template <int RB>
-__device__ __forceinline__ typename RowMask<RB>::T load_row_bits(const void *rows, int64_t ri) {
-    uint4 q = make_uint4(0, 0, 0, 0);
-    if constexpr (RB == 16) {
-        q = reinterpret_cast<const uint4 *>(rows)[ri];
-    } else if constexpr (RB == 8) {
-        const uint64_t v = reinterpret_cast<const uint64_t *>(rows)[ri];
-        q.x = (uint32_t)v;
-        q.y = (uint32_t)(v >> 32);
-    } else if constexpr (RB == 4) {
-        q.x = reinterpret_cast<const uint32_t *>(rows)[ri];
-    } else {
-        q.x = reinterpret_cast<const uint16_t *>(rows)[ri];
-    }
-    typename RowMask<RB>::T t;
-    bool cnt, sg;
-    row_in_word<RB>(q, 0, t, cnt, sg);
-    return t;
-}
-
-// a load that sees what other lanes of this wave stored before the fence
-template <class T>
-__device__ __forceinline__ T load_fresh(const T *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int64_t choose2(int64_t n) { return n * (n - 1) / 2; }
-
-}  // namespace
-
-template <int RB>
-__global__ __launch_bounds__(256) void window_xpnsl_kernel(DevParams P, const void *__restrict__ rows, uint32_t n_rows,
-                                                           uint32_t n_win, XpnslArgs A) {
+struct XpnslWalk {
     using M = typename RowMask<RB>::T;
-    using Q = QueuedRow<RB>;
-    using QT = typename Q::T;
-    constexpr int R = 16 / RB;
-    extern __shared__ uint4 s_xpnsl[];
-    const int np = P.npops, npairs = np * (np - 1) / 2, tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint64_t ch = (uint64_t)blockIdx.x * (uint64_t)A.waves + (uint64_t)wave;
-    if (ch >= (uint64_t)n_win * (uint64_t)npairs) return;   // the whole wave
-    // this wave's LDS: [queue bits 64 * R][queue rows 64 * R][last: pairs_max][uv: pairs_max][pos: 128]
-    unsigned char *base = reinterpret_cast<unsigned char *>(s_xpnsl) + (size_t)wave * A.wave_bytes;
-    QT *qx = reinterpret_cast<QT *>(base);
-    int32_t *qrow = reinterpret_cast<int32_t *>(qx + 64 * R);
-    int32_t *last = qrow + 64 * R;
-    uint16_t *uv = reinterpret_cast<uint16_t *>(last + A.pairs_max);
-    uint8_t *pos = reinterpret_cast<uint8_t *>(uv + ((A.pairs_max + 1) & ~1));
-
-    const uint32_t w = (uint32_t)(ch / (uint64_t)npairs);
-    int pi = 0, pj = (int)(ch - (uint64_t)w * (uint64_t)npairs);   // pair (pi, pj), pi < pj, lexicographic
-    while (pj >= np - 1 - pi) {
-        pj -= np - 1 - pi;
-        ++pi;
-    }
-    pj += pi + 1;
-    const int n0 = P.pop_n[pi], n1 = P.pop_n[pj], nn = n0 + n1, ms = A.max_sites;
-    const M pm0 = pop_mask<M>(P, pi), pm1 = pop_mask<M>(P, pj), pmu = join(pm0, pm1);
-    const WindowRows win = clamp_window(A.wins[w], n_rows, A.err, lane);
-    const size_t s0 = (size_t)ch * (size_t)ms;   // the chain's first slot
-    int32_t *o_row = A.row ? A.row + s0 : nullptr, *o_m = A.m ? A.m + s0 * 2 : nullptr;
-    int64_t *o_sl = A.sl ? A.sl + s0 * 2 : nullptr;
-    int32_t *o_cens = A.cens ? A.cens + s0 * 2 : nullptr;
-
-    // count
-    uint32_t nv = 0;
-    if (!win.empty)
-        gather_rows_in_order<RB, 4>(
-            rows, n_rows, win, lane,
-            [&](M &t, bool, bool sg) {
-                const int m = (int)pc(t & pmu);
-                nv += (sg && m >= 1 && m <= nn - 1) ? 1u : 0u;
-                return false;
-            },
-            [&](uint32_t, const M &, int64_t) {}, [&](uint32_t) {});
-    const int V = (int)wave_sum32(nv);
-    if (lane == 0 && A.n_var) A.n_var[ch] = V;
-    if (ms == 0) return;
-    const bool fits = V <= ms;
-    for (int k = (fits ? V : 0) + lane; k < ms; k += 64) {   // the unused slots
-        if (o_row) o_row[k] = -1;
-        if (o_m) o_m[2 * (size_t)k] = o_m[2 * (size_t)k + 1] = 0;
-        if (o_sl) o_sl[2 * (size_t)k] = o_sl[2 * (size_t)k + 1] = 0;
-        if (o_cens) o_cens[2 * (size_t)k] = o_cens[2 * (size_t)k + 1] = 0;
-    }
-    if (!fits || V == 0) return;
-
-    const int C0 = n0 * (n0 - 1) / 2, C1 = n1 * (n1 - 1) / 2, Pn = C0 + C1;   // 0 when both sides are one sample
-    const bool walks = (o_sl || o_cens) && o_row;
-    // a site's sum over the wave stays below 2^32 when every distance is at most V + 1: one scan
-    const bool narrow = ((uint64_t)V + 1) * (uint64_t)(Pn > 0 ? Pn : 1) < (1ULL << 32);
-    if (walks && Pn > 0) {
-        if (!PBG_STORE_OK(A.err, Pn - 1, A.pairs_max, A.pairs_max, kErrPool)) return;   // wave-uniform
-        // the pair table: each side's samples by ascending bit, then its pairs (u, v), u < v; side 0 first
-        for (int l = lane; l < (RB == 16 ? 128 : 64); l += 64) {
-            if (bit(pm0, l)) pos[rank_below(pm0, l)] = (uint8_t)l;
-            else if (bit(pm1, l)) pos[n0 + rank_below(pm1, l)] = (uint8_t)l;
-        }
-        wave_sync();
-        auto fill = [&](int n, int pos0, int pair0, int Cn) {
-            int u = 0, v = 1;
-            auto advance = [&](int d) {   // d pairs on; the target exists
-                while (d > 0) {
-                    const int room = n - 1 - v;
-                    if (d <= room) {
-                        v += d;
-                        d = 0;
-                    } else {
-                        d -= room + 1;
-                        ++u;
-                        v = u + 1;
-                    }
-                }
-            };
-            if (lane < Cn) advance(lane);
-            for (int p = lane; p < Cn; p += 64) {
-                uv[pair0 + p] = (uint16_t)(pos[pos0 + u] | (uint32_t)pos[pos0 + v] << 8);
-                last[pair0 + p] = -1;
-                if (p + 64 < Cn) advance(64);
-            }
-        };
-        fill(n0, 0, 0, C0);
-        fill(n1, n0, C0, C1);
-        wave_sync();
-    }
-
+    static constexpr int kM = 2;
+    struct Tot {
+        uint64_t s0, s1;   // the sides' sums
+        uint32_t c0, c1;   // the sides' agreeing pairs still at the walk's start value
+    };
+    M pm0, pm1, pm;
+    int n0, n1, C0, C1, Pn, lane;   // Pn = C0 + C1: 0 when both sides are one sample
+    int32_t *last;
+    const uint16_t *uv;
     // the walk's state per side, wave-uniform: the sum of last[] and the pairs still at the start value
-    int64_t sum0 = -(int64_t)C0, sum1 = -(int64_t)C1;
-    int32_t ne0 = C0, ne1 = C1;
+    int64_t sum0, sum1;
+    int32_t ne0, ne1;
+    bool narrow;   // a site's sum over the wave stays below 2^32 when every distance is at most V + 1: one scan
 
-    // one site of a walk against column x: per side the sum of |k - last| over its agreeing pairs and
-    // those of them whose last is still `edge`; a differing pair moves last to k
-    auto site = [&](const M &x, int k, int edge, uint64_t &t0, uint64_t &t1, uint32_t &c0, uint32_t &c1) {
+    __device__ __forceinline__ bool is_site(const M &x) const {
+        const int m = (int)pc(x);
+        return m >= 1 && m <= n0 + n1 - 1;
+    }
+    __device__ __forceinline__ void pairs(const TractLds<RB> &L) const {
+        tract_pairs(L, lane, pm0, n0, 0, 0);
+        tract_pairs(L, lane, pm1, n1, n0, C0);
+    }
+    __device__ __forceinline__ void store_m(int32_t *o, const M &x) const {
+        o[0] = (int32_t)pc(x & pm0);
+        o[1] = (int32_t)pc(x & pm1);
+    }
+    __device__ __forceinline__ void start(int V, int edge) {
+        narrow = ((uint64_t)V + 1) * (uint64_t)(Pn > 0 ? Pn : 1) < (1ULL << 32);
+        sum0 = (int64_t)C0 * edge;
+        sum1 = (int64_t)C1 * edge;
+        ne0 = C0;
+        ne1 = C1;
+    }
+
+    // per side the sum of |k - last| over its agreeing pairs and those of them whose last is still
+    // `edge`; a differing pair moves last to k
+    __device__ __forceinline__ Tot site(const M &x, int k, int edge) {
         const int m0 = __builtin_amdgcn_readfirstlane((int)pc(x & pm0));
         const int m1 = __builtin_amdgcn_readfirstlane((int)pc(x & pm1));
 #ifdef PBG_XPNSL_PLAIN   // an experiment switch: the timing variant without the shortcut
@@ -241,138 +128,77 @@ __global__ __launch_bounds__(256) void window_xpnsl_kernel(DevParams P, const vo
                 de1 = wave_sum32(e1);
             }
         }
-        t0 = (uint64_t)all0 - dd0;
-        t1 = (uint64_t)all1 - dd1;
-        c0 = (uint32_t)ne0 - de0;
-        c1 = (uint32_t)ne1 - de1;
+        const Tot t{(uint64_t)all0 - dd0, (uint64_t)all1 - dd1, (uint32_t)ne0 - de0, (uint32_t)ne1 - de1};
         sum0 += fwd ? (int64_t)dd0 : -(int64_t)dd0;
         sum1 += fwd ? (int64_t)dd1 : -(int64_t)dd1;
         ne0 -= (int32_t)de0;
         ne1 -= (int32_t)de1;
-    };
-
-    // forward
-    int kbase = 0;   // wave-uniform: the sites before this trip
-    stream_rows_in_order<RB, 4>(
-        rows, n_rows, win, lane, qx, qrow,
-        [&](M &t) -> bool {
-            t = t & pmu;
-            const int m = (int)pc(t);
-            return m >= 1 && m <= nn - 1;
-        },
-        [&](int nq) {
-            for (int j = lane; j < nq; j += 64)
-                if (PBG_STORE_OK(A.err, kbase + j, ms, ms, kErrPool)) {
-                    if (o_row) o_row[kbase + j] = qrow[j];
-                    if (o_m) {
-                        const M x = Q::get(qx[j]);
-                        o_m[2 * (size_t)(kbase + j)] = (int32_t)pc(x & pm0);
-                        o_m[2 * (size_t)(kbase + j) + 1] = (int32_t)pc(x & pm1);
-                    }
-                }
-            if (walks)
-                for (int c0 = 0; c0 < nq; c0 += 64) {
-                    const int cnt = nq - c0 < 64 ? nq - c0 : 64;
-                    uint64_t r0 = 0, r1 = 0;
-                    uint32_t rc0 = 0, rc1 = 0;
-                    for (int kk = 0; kk < cnt; ++kk) {
-                        uint64_t t0, t1;
-                        uint32_t tc0, tc1;
-                        site(Q::get(qx[c0 + kk]), kbase + c0 + kk, -1, t0, t1, tc0, tc1);
-                        if (lane == kk) {
-                            r0 = t0;
-                            r1 = t1;
-                            rc0 = tc0;
-                            rc1 = tc1;
-                        }
-                    }
-                    const int k = kbase + c0 + lane;
-                    if (lane < cnt && PBG_STORE_OK(A.err, k, ms, ms, kErrPool)) {
-                        if (o_sl) {
-                            o_sl[2 * (size_t)k] = (int64_t)r0;
-                            o_sl[2 * (size_t)k + 1] = (int64_t)r1;
-                        }
-                        if (o_cens) {
-                            o_cens[2 * (size_t)k] = (int32_t)rc0;
-                            o_cens[2 * (size_t)k + 1] = (int32_t)rc1;
-                        }
-                    }
-                }
-            kbase += nq;
-        });
-    if (!walks) return;
-
-    // backward
-    __threadfence();   // row[] and the left sums, stored by other lanes of this wave
-    for (int p = lane; p < Pn; p += 64) last[p] = V;
-    sum0 = (int64_t)C0 * V;
-    sum1 = (int64_t)C1 * V;
-    ne0 = C0;
-    ne1 = C1;
-    auto fetch = [&](int k0) -> M {   // the column of site k0 + lane
-        const int k = k0 + lane;
-        if (k0 < 0 || k >= V) return M{};
-        const int32_t r = load_fresh(o_row + k);
-        if (r < 0 || (uint32_t)r >= n_rows) return M{};   // never: a row index this chain stored
-        return load_row_bits<RB>(rows, r) & pmu;
-    };
-    int k0 = ((V - 1) / 64) * 64;
-    M xc = fetch(k0);
-    for (; k0 >= 0; k0 -= 64) {
-        const int cnt = V - k0 < 64 ? V - k0 : 64;
-        const M xn = fetch(k0 - 64);
-        qx[lane] = Q::put(xc);
-        wave_sync();
-        uint64_t r0 = 0, r1 = 0;
-        uint32_t rc0 = 0, rc1 = 0;
-        for (int kk = cnt - 1; kk >= 0; --kk) {
-            uint64_t t0, t1;
-            uint32_t tc0, tc1;
-            site(Q::get(qx[kk]), k0 + kk, V, t0, t1, tc0, tc1);
-            if (lane == kk) {
-                r0 = t0;
-                r1 = t1;
-                rc0 = tc0;
-                rc1 = tc1;
-            }
-        }
-        const int k = k0 + lane;
-        if (lane < cnt && PBG_STORE_OK(A.err, k, ms, ms, kErrPool)) {
-            if (o_sl) {
-                const int64_t m0 = (int64_t)pc(xc & pm0), m1 = (int64_t)pc(xc & pm1);
-                o_sl[2 * (size_t)k] = load_fresh(o_sl + 2 * (size_t)k) + (int64_t)r0 - choose2(m0) - choose2(n0 - m0);
-                o_sl[2 * (size_t)k + 1] = load_fresh(o_sl + 2 * (size_t)k + 1) + (int64_t)r1 - choose2(m1) - choose2(n1 - m1);
-            }
-            if (o_cens) {
-                o_cens[2 * (size_t)k] = load_fresh(o_cens + 2 * (size_t)k) + (int32_t)rc0;
-                o_cens[2 * (size_t)k + 1] = load_fresh(o_cens + 2 * (size_t)k + 1) + (int32_t)rc1;
-            }
-        }
-        wave_sync();   // the next trip's queue
-        xc = xn;
+        return t;
     }
+
+    __device__ __forceinline__ void store_fwd(const TractOut &O, int k, const Tot &r) const {
+        if (O.sl) {
+            O.sl[2 * (size_t)k] = (int64_t)r.s0;
+            O.sl[2 * (size_t)k + 1] = (int64_t)r.s1;
+        }
+        if (O.cens) {
+            O.cens[2 * (size_t)k] = (int32_t)r.c0;
+            O.cens[2 * (size_t)k + 1] = (int32_t)r.c1;
+        }
+    }
+    __device__ __forceinline__ void store_bwd(const TractOut &O, int k, const Tot &r, const M &x) const {
+        if (O.sl) {
+            const int64_t m0 = (int64_t)pc(x & pm0), m1 = (int64_t)pc(x & pm1);
+            O.sl[2 * (size_t)k] = load_fresh(O.sl + 2 * (size_t)k) + (int64_t)r.s0 - choose2(m0) - choose2(n0 - m0);
+            O.sl[2 * (size_t)k + 1] = load_fresh(O.sl + 2 * (size_t)k + 1) + (int64_t)r.s1 - choose2(m1) - choose2(n1 - m1);
+        }
+        if (O.cens) {
+            O.cens[2 * (size_t)k] = load_fresh(O.cens + 2 * (size_t)k) + (int32_t)r.c0;
+            O.cens[2 * (size_t)k + 1] = load_fresh(O.cens + 2 * (size_t)k + 1) + (int32_t)r.c1;
+        }
+    }
+};
+
+}  // namespace
+
+template <int RB>
+__global__ __launch_bounds__(256) void window_xpnsl_kernel(DevParams P, const void *__restrict__ rows, uint32_t n_rows,
+                                                           uint32_t n_win, TractArgs A) {
+    using M = typename RowMask<RB>::T;
+    extern __shared__ uint4 s_xpnsl[];
+    const int np = P.npops, npairs = np * (np - 1) / 2, tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint64_t ch = (uint64_t)blockIdx.x * (uint64_t)A.waves + (uint64_t)wave;
+    if (ch >= (uint64_t)n_win * (uint64_t)npairs) return;   // the whole wave
+    const TractLds<RB> L(reinterpret_cast<unsigned char *>(s_xpnsl) + (size_t)wave * A.wave_bytes, A.pairs_max);
+    const uint32_t w = (uint32_t)(ch / (uint64_t)npairs);
+    int pi = 0, pj = (int)(ch - (uint64_t)w * (uint64_t)npairs);   // pair (pi, pj), pi < pj, lexicographic
+    while (pj >= np - 1 - pi) {
+        pj -= np - 1 - pi;
+        ++pi;
+    }
+    pj += pi + 1;
+    const int n0 = P.pop_n[pi], n1 = P.pop_n[pj], C0 = n0 * (n0 - 1) / 2, C1 = n1 * (n1 - 1) / 2;
+    const M pm0 = pop_mask<M>(P, pi), pm1 = pop_mask<M>(P, pj);
+    XpnslWalk<RB> pol{pm0, pm1, join(pm0, pm1), n0, n1, C0, C1, C0 + C1, lane, L.last, L.uv, 0, 0, 0, 0, false};
+    tract_chain<RB>(rows, n_rows, clamp_window(A.wins[w], n_rows, A.err, lane), lane, A, ch, L, pol);
 }
 
-hipError_t launch_window_xpnsl(int rb, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win, XpnslArgs A,
+hipError_t launch_window_xpnsl(int rb, const DevParams &P, const void *rows, uint32_t n_rows, uint32_t n_win, TractArgs A,
                                hipStream_t stream) {
     const int npairs = P.npops * (P.npops - 1) / 2;
     if (n_win == 0 || npairs == 0) return hipSuccess;
     // both sides' pairs share a chain's table; the populations are disjoint and hold at most 126 samples,
     // so the largest C(n_i, 2) + C(n_j, 2) is at most C(126, 2), pbg_window_nsl's own worst case
-    A.pairs_max = 1;
+    int pairs_max = 1;
     for (int i = 0; i < P.npops; ++i)
         for (int j = i + 1; j < P.npops; ++j) {
-            const int c = P.pop_n[i] * (P.pop_n[i] - 1) / 2 + P.pop_n[j] * (P.pop_n[j] - 1) / 2;
-            A.pairs_max = c > A.pairs_max ? c : A.pairs_max;
+            const int c = (int)(choose2(P.pop_n[i]) + choose2(P.pop_n[j]));
+            pairs_max = c > pairs_max ? c : pairs_max;
         }
-    const size_t wb = nsl_wave_bytes(rb, A.pairs_max);   // the same per-wave layout
-    if (wb > 64 * 1024) return hipErrorInvalidValue;   // never: 7,875 pairs take 48,672 bytes
-    A.wave_bytes = (uint32_t)wb;
-    A.waves = 4 * wb <= 64 * 1024 ? 4 : 2 * wb <= 64 * 1024 ? 2 : 1;
-    const uint64_t chains = (uint64_t)n_win * (uint64_t)npairs;
-    const dim3 g((uint32_t)((chains + A.waves - 1) / A.waves)), b(64 * A.waves);
+    TractPlan plan;
+    if (!tract_plan(rb, pairs_max, (uint64_t)n_win * (uint64_t)npairs, A, plan)) return hipErrorInvalidValue;
     dispatch_rb(rb, [&](auto RB) {
-        hipLaunchKernelGGL(window_xpnsl_kernel<decltype(RB)::value>, g, b, (size_t)A.waves * wb, stream, P, rows, n_rows,
+        hipLaunchKernelGGL(window_xpnsl_kernel<decltype(RB)::value>, plan.grid, plan.block, plan.lds, stream, P, rows, n_rows,
                            n_win, A);
     });
     return hipGetLastError();

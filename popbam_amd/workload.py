@@ -143,11 +143,34 @@ class WindowOutputs:
         return o
 
 
-class LdDecay:
+class _WindowCall:
+    """One window entry point on packed rows.  A subclass names it (ENTRY), owns its device arrays and
+    builds `out` and, when the entry point takes options, `opts`."""
+
+    ENTRY = ""
+    opts = None
+
+    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
+        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
+        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
+        if n_rows is None:
+            n_rows = rows.numel() // self.ctx.row_bytes
+        opts = () if self.opts is None else (C.byref(self.opts),)
+        return getattr(self.ctx.lib, self.ENTRY)(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win, *opts,
+                                                 C.byref(self.out), stream_handle(stream))
+
+    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
+        self.ctx.check(self.run(rows, wins, n_rows, stream), self.ENTRY)
+        return self
+
+
+class LdDecay(_WindowCall):
     """pbg_window_ld_decay: r^2 binned by the distance between variable sites, per window and
     population.  Owns the three device arrays -- pairs[n_win, n_pops, n_bins] (int64),
     r2_sum[n_win, n_pops, n_bins] (float64), n_var[n_win, n_pops] (int32) -- and runs on a
     HotPath's rows and windows, or on any rows tensor with a window list."""
+
+    ENTRY = "pbg_window_ld_decay"
 
     def __init__(self, ctx: _lib.Context, n_win: int, bin_bp: int, n_bins: int, min_freq: int = 1,
                  device: str = "cuda"):
@@ -159,18 +182,6 @@ class LdDecay:
         self.n_var = torch.zeros((n_win, np_), dtype=torch.int32, device=device)
         self.out = _lib.PbgDecayOut(_ptr(self.pairs), _ptr(self.r2_sum), _ptr(self.n_var))
 
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_ld_decay(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                                C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_ld_decay")
-        return self
-
     @classmethod
     def of(cls, hp: "HotPath", bin_bp: int, n_bins: int, min_freq: int = 1, stream=None) -> "LdDecay":
         """The decay of a HotPath's rows over its windows (after hp.call)."""
@@ -178,13 +189,15 @@ class LdDecay:
             hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
-class JointSfs:
+class JointSfs(_WindowCall):
     """pbg_window_jsfs: the joint site-frequency spectrum, the pairwise-difference counts and
     Hudson's Fst per window and population pair i < j.  Owns the three device arrays --
     cells[n_win, C] (int32, C = pbg_jsfs_cells: pair p's (n_i+1) x (n_j+1) block at pair_offset),
     diffs[n_win, n_pairs, 3] (int64: SW_i, SW_j, SB), fst[n_win, n_pairs] (float64) -- and runs
     on a HotPath's rows and windows, or on any rows tensor with a window list.  `outidx` counts
     only when the context has PBG_F_OUTGROUP."""
+
+    ENTRY = "pbg_window_jsfs"
 
     def __init__(self, ctx: _lib.Context, n_win: int, outidx: int = 0, device: str = "cuda"):
         self.ctx, self.n_win = ctx, n_win
@@ -200,30 +213,20 @@ class JointSfs:
     def pair_offset(self, i: int, j: int) -> int:
         return self.ctx.check(self.ctx.lib.pbg_jsfs_pair_offset(self.ctx.h, i, j), "pbg_jsfs_pair_offset")
 
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_jsfs(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                            C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_jsfs")
-        return self
-
     @classmethod
     def of(cls, hp: "HotPath", outidx: int = 0, stream=None) -> "JointSfs":
         """The joint spectra of a HotPath's rows over its windows (after hp.call)."""
         return cls(hp.ctx, hp.n_win, outidx, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
-class DStat:
+class DStat(_WindowCall):
     """pbg_window_dstat: Patterson's D (ABBA-BABA), f_d and f_dM per window and population triple.
     `triples` is a list of (p1, p2, p3) population indices (a host array of the call).  Owns the
     four device arrays -- sums[n_win, n_triples, 6] (int64: ABBA, BABA, FD2, FD3, GD1, GD3) and
     d, fd, fdm[n_win, n_triples] (float64) -- and runs on a HotPath's rows and windows, or on any
     rows tensor with a window list.  `outidx` counts only when the context has PBG_F_OUTGROUP."""
+
+    ENTRY = "pbg_window_dstat"
 
     def __init__(self, ctx: _lib.Context, n_win: int, triples, outidx: int = 0, device: str = "cuda"):
         self.ctx, self.n_win = ctx, n_win
@@ -237,25 +240,13 @@ class DStat:
         self.fdm = torch.zeros((n_win, self.n_triples), dtype=torch.float64, device=device)
         self.out = _lib.PbgDstatOut(_ptr(self.sums), _ptr(self.d), _ptr(self.fd), _ptr(self.fdm))
 
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_dstat(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                             C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_dstat")
-        return self
-
     @classmethod
     def of(cls, hp: "HotPath", triples, outidx: int = 0, stream=None) -> "DStat":
         """The D statistics of a HotPath's rows over its windows (after hp.call)."""
         return cls(hp.ctx, hp.n_win, triples, outidx, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
-class Hfs:
+class Hfs(_WindowCall):
     """pbg_window_hfs: the haplotype frequency spectrum, Garud's H statistics and the haplotype
     diversity per window and population.  Owns the five device arrays -- k[n_win, n_pops] (int32),
     counts[n_win, n_pops, stride] (int32, sorted descending, stride = the largest population),
@@ -264,6 +255,8 @@ class Hfs:
     windows, or on any rows tensor with a window list."""
 
     NAMES = ("k", "counts", "cls", "sums", "h")
+
+    ENTRY = "pbg_window_hfs"
 
     def __init__(self, ctx: _lib.Context, n_win: int, device: str = "cuda"):
         self.ctx, self.n_win = ctx, n_win
@@ -276,31 +269,21 @@ class Hfs:
         self.h = torch.zeros((n_win, np_, 5), dtype=torch.float64, device=device)
         self.out = _lib.PbgHfsOut(*(_ptr(getattr(self, k)) for k in self.NAMES))
 
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_hfs(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                           C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_hfs")
-        return self
-
     @classmethod
     def of(cls, hp: "HotPath", stream=None) -> "Hfs":
         """The haplotype spectrum of a HotPath's rows over its windows (after hp.call)."""
         return cls(hp.ctx, hp.n_win, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
-class Rmin:
+class Rmin(_WindowCall):
     """pbg_window_rmin: Hudson and Kaplan's Rm and its intervals per window and population.  Owns the
     three device arrays -- rmin[n_win, n_pops] and n_var[n_win, n_pops] (int32) and, with max_cuts > 0,
     cuts[n_win, n_pops, max_cuts, 2] (int32: the chosen intervals' (left row, right row), then
     (-1, -1)) -- and runs on a HotPath's rows and windows, or on any rows tensor with a window list."""
 
     NAMES = ("rmin", "n_var", "cuts")
+
+    ENTRY = "pbg_window_rmin"
 
     def __init__(self, ctx: _lib.Context, n_win: int, min_freq: int = 1, max_cuts: int = 0, device: str = "cuda"):
         self.ctx, self.n_win = ctx, n_win
@@ -311,104 +294,78 @@ class Rmin:
         self.cuts = torch.zeros((n_win, np_, max(max_cuts, 0), 2), dtype=torch.int32, device=device)
         self.out = _lib.PbgRminOut(_ptr(self.rmin), _ptr(self.n_var), _ptr(self.cuts) if max_cuts > 0 else None)
 
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_rmin(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                            C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_rmin")
-        return self
-
     @classmethod
     def of(cls, hp: "HotPath", min_freq: int = 1, max_cuts: int = 0, stream=None) -> "Rmin":
         """Rm of a HotPath's rows over its windows (after hp.call)."""
         return cls(hp.ctx, hp.n_win, min_freq, max_cuts, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
 
 
-class Nsl:
+class _Tract(_WindowCall):
+    """A per-site tract call (pbg_tract.h): its chains are a function of the populations, and every chain
+    has n_var sites and, with max_sites > 0, max_sites slots of row, m, sl and cens.  A subclass states its
+    entry point, its ctypes pair, its chains per window and m's trailing shape."""
+
+    NAMES = ("n_var", "row", "m", "sl", "cens")
+    OPTS = OUT = None
+    M_SHAPE = ()
+
+    @staticmethod
+    def chains(n_pops: int) -> int:
+        raise NotImplementedError
+
+    def __init__(self, ctx: _lib.Context, n_win: int, max_sites: int = 0, device: str = "cuda"):
+        self.ctx, self.n_win = ctx, n_win
+        self.n_chains = nc = self.chains(ctx.params.n_pops)
+        ms = max(max_sites, 0)
+        self.opts = self.OPTS(max_sites, 0)
+        self.n_var = torch.zeros((n_win, nc), dtype=torch.int32, device=device)
+        self.row = torch.zeros((n_win, nc, ms), dtype=torch.int32, device=device)
+        self.m = torch.zeros((n_win, nc, ms, *self.M_SHAPE), dtype=torch.int32, device=device)
+        self.sl = torch.zeros((n_win, nc, ms, 2), dtype=torch.int64, device=device)
+        self.cens = torch.zeros((n_win, nc, ms, 2), dtype=torch.int32, device=device)
+        per_site = [_ptr(t) if max_sites > 0 else None for t in (self.row, self.m, self.sl, self.cens)]
+        self.out = self.OUT(_ptr(self.n_var), *per_site)
+
+    @classmethod
+    def of(cls, hp: "HotPath", max_sites: int = 0, stream=None):
+        """The tract sums of a HotPath's rows over its windows (after hp.call)."""
+        return cls(hp.ctx, hp.n_win, max_sites, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+
+
+class Nsl(_Tract):
     """pbg_window_nsl: the per-site nSL tract sums per window and population.  Owns the device arrays --
     n_var[n_win, n_pops] (int32) and, with max_sites > 0, row and m[n_win, n_pops, max_sites] (int32),
     sl[n_win, n_pops, max_sites, 2] (int64) and cens[n_win, n_pops, max_sites, 2] (int32) -- and runs on
     a HotPath's rows and windows, or on any rows tensor with a window list.  max_sites = 0 is the
     count-only call."""
 
-    NAMES = ("n_var", "row", "m", "sl", "cens")
+    ENTRY, OPTS, OUT = "pbg_window_nsl", _lib.PbgNslOpts, _lib.PbgNslOut
 
-    def __init__(self, ctx: _lib.Context, n_win: int, max_sites: int = 0, device: str = "cuda"):
-        self.ctx, self.n_win = ctx, n_win
-        np_, ms = ctx.params.n_pops, max(max_sites, 0)
-        self.opts = _lib.PbgNslOpts(max_sites, 0)
-        self.n_var = torch.zeros((n_win, np_), dtype=torch.int32, device=device)
-        self.row = torch.zeros((n_win, np_, ms), dtype=torch.int32, device=device)
-        self.m = torch.zeros((n_win, np_, ms), dtype=torch.int32, device=device)
-        self.sl = torch.zeros((n_win, np_, ms, 2), dtype=torch.int64, device=device)
-        self.cens = torch.zeros((n_win, np_, ms, 2), dtype=torch.int32, device=device)
-        per_site = [_ptr(t) if max_sites > 0 else None for t in (self.row, self.m, self.sl, self.cens)]
-        self.out = _lib.PbgNslOut(_ptr(self.n_var), *per_site)
-
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_nsl(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                           C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_nsl")
-        return self
-
-    @classmethod
-    def of(cls, hp: "HotPath", max_sites: int = 0, stream=None) -> "Nsl":
-        """The tract sums of a HotPath's rows over its windows (after hp.call)."""
-        return cls(hp.ctx, hp.n_win, max_sites, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+    @staticmethod
+    def chains(n_pops: int) -> int:
+        return n_pops
 
 
-class Xpnsl:
+class Xpnsl(_Tract):
     """pbg_window_xpnsl: the cross-population nSL tract sums per window and population pair (i < j,
     lexicographic).  Owns the device arrays -- n_var[n_win, n_pairs] (int32) and, with max_sites > 0,
     row[n_win, n_pairs, max_sites] (int32), m and cens[n_win, n_pairs, max_sites, 2] (int32) and
     sl[n_win, n_pairs, max_sites, 2] (int64), the last index the side -- and runs on a HotPath's rows and
     windows, or on any rows tensor with a window list.  max_sites = 0 is the count-only call."""
 
-    NAMES = ("n_var", "row", "m", "sl", "cens")
+    ENTRY, OPTS, OUT = "pbg_window_xpnsl", _lib.PbgXpnslOpts, _lib.PbgXpnslOut
+    M_SHAPE = (2,)
 
-    def __init__(self, ctx: _lib.Context, n_win: int, max_sites: int = 0, device: str = "cuda"):
-        self.ctx, self.n_win = ctx, n_win
-        np_, ms = ctx.params.n_pops, max(max_sites, 0)
-        self.n_pairs = npr = np_ * (np_ - 1) // 2
-        self.opts = _lib.PbgXpnslOpts(max_sites, 0)
-        self.n_var = torch.zeros((n_win, npr), dtype=torch.int32, device=device)
-        self.row = torch.zeros((n_win, npr, ms), dtype=torch.int32, device=device)
-        self.m = torch.zeros((n_win, npr, ms, 2), dtype=torch.int32, device=device)
-        self.sl = torch.zeros((n_win, npr, ms, 2), dtype=torch.int64, device=device)
-        self.cens = torch.zeros((n_win, npr, ms, 2), dtype=torch.int32, device=device)
-        per_site = [_ptr(t) if max_sites > 0 else None for t in (self.row, self.m, self.sl, self.cens)]
-        self.out = _lib.PbgXpnslOut(_ptr(self.n_var), *per_site)
+    @staticmethod
+    def chains(n_pops: int) -> int:
+        return n_pops * (n_pops - 1) // 2
 
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_xpnsl(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                             C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_xpnsl")
-        return self
-
-    @classmethod
-    def of(cls, hp: "HotPath", max_sites: int = 0, stream=None) -> "Xpnsl":
-        """The tract sums of a HotPath's rows over its windows (after hp.call)."""
-        return cls(hp.ctx, hp.n_win, max_sites, str(hp.rows.device))(hp.rows, hp.wins, hp.synth.n_sites, stream)
+    @property
+    def n_pairs(self) -> int:
+        return self.n_chains
 
 
-class Snn:
+class Snn(_WindowCall):
     """pbg_window_snn: the exact sample-by-sample difference matrix of every window and Hudson's Snn with
     its permutation test per window and group of populations.  `groups` is a list of population-index
     collections (a host array of the call; default_groups gives the command line's).  Owns the device
@@ -418,6 +375,8 @@ class Snn:
     tensor with a window list.  No groups is the difference matrix alone."""
 
     NAMES = ("diff", "snn", "near", "ge")
+
+    ENTRY = "pbg_window_snn"
 
     def __init__(self, ctx: _lib.Context, n_win: int, groups=(), n_perms: int = 1000, seed: int = 0, key0: int = 0,
                  device: str = "cuda"):
@@ -445,18 +404,6 @@ class Snn:
     def chunks(self) -> int:
         """The permutation chunks the call runs per (window, group)."""
         return self.ctx.lib.pbg_snn_chunks(self.n_win, self.n_groups, self.n_perms)
-
-    def run(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None) -> int:
-        """Enqueue the call on `rows` (u8 device tensor of packed rows) and `wins` (int32 device
-        tensor of n_win (beg, end) pairs); returns the entry point's status without raising."""
-        if n_rows is None:
-            n_rows = rows.numel() // self.ctx.row_bytes
-        return self.ctx.lib.pbg_window_snn(self.ctx.h, _ptr(rows), n_rows, _ptr(wins), self.n_win,
-                                           C.byref(self.opts), C.byref(self.out), stream_handle(stream))
-
-    def __call__(self, rows: torch.Tensor, wins: torch.Tensor, n_rows: int | None = None, stream=None):
-        self.ctx.check(self.run(rows, wins, n_rows, stream), "pbg_window_snn")
-        return self
 
     @classmethod
     def of(cls, hp: "HotPath", groups=(), n_perms: int = 1000, seed: int = 0, key0: int = 0, stream=None) -> "Snn":

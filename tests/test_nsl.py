@@ -10,37 +10,26 @@ Python's math.log of the same two divisions."""
 import ctypes as C
 import math
 import os
-import subprocess
-import sys
+from functools import partial
 
 import numpy as np
 import pytest
 
 import fixtures
 import harness
-from window_helpers import _arrays, _blocks, mask_words, _native, _wins_tensor
+import tract_helpers
+from tract_helpers import BOUNDS_LIB, COUNTED, NAMES, N_SITES, SEED, SEG, SHAPES, WIDE
+from tract_helpers import local_bits, row_ints, _assert_same, _founder_cols, _params, _shape, _windows, _run_nsl
+from tract_helpers import _founder_types, _crafted, _padded, _interleaving, _bounds_child
+from window_helpers import _arrays, _blocks, _native, _wins_tensor
 from window_helpers import PARTIAL_WORD_CASES, partial_rows
 from popbam_amd import cli
 from popbam_amd import options as opt
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BOUNDS_LIB = os.path.join(REPO, "popbam_amd", "variants", "bounds", "libpopbam_gpu.so")
-SEED = 0x4A1   # test_rmin.py's: the same called rows
-COUNTED, SEG = 2, 4   # harness flags bits
-NAMES = ("n_var", "row", "m", "sl", "cens")
+_run_sized = partial(tract_helpers._run_sized, run=_run_nsl)
 
 
 # ---- the checker -----------------------------------------------------------------------
-def local_bits(x, pm):
-    """The bits of column x at the samples of mask pm, by ascending sample id."""
-    out, s = [], 0
-    while pm >> s:
-        if (pm >> s) & 1:
-            out.append((x >> s) & 1)
-        s += 1
-    return out
-
-
 def chain_scalar(cols):
     """The definition.  cols[k]: the population's bits at variable site k.  -> per site (sl0, sl1, cens0,
     cens1)."""
@@ -134,11 +123,6 @@ def chain_runs(cols):
     return [tuple(r) for r in res], sq
 
 
-def row_ints(types):
-    lo, hi = mask_words(types)
-    return [int(a) | (int(b) << 64) for a, b in zip(lo.tolist(), hi.tolist())]
-
-
 def variable_sites(ints, seg, pm, n_i, beg, end):
     """[(row, column)] of a chain: segregating rows of [beg, end) with 1 <= m <= n_i - 1."""
     rows = (beg + np.flatnonzero(seg[beg:end])).tolist()
@@ -179,25 +163,6 @@ def value_text(n_i, m, sl0, sl1):
     if p0 == 0 or p1 == 0:
         return "NA"
     return "%.5f" % math.log((float(sl0) / float(p0)) / (float(sl1) / float(p1)))
-
-
-def _assert_same(got, want, what=""):
-    for g, w, nm in zip(got, want, NAMES):
-        assert g.shape == w.shape and g.dtype == w.dtype, (what, nm, g.shape, w.shape, g.dtype, w.dtype)
-        same = g == w
-        assert same.all(), (what, nm, np.argwhere(~same)[:5].tolist(), g[~same][:5], w[~same][:5])
-
-
-def _founder_cols(rng, V, n, founders, stretch):
-    """Columns in which every sample copies one of a few founders, the copy changing every `stretch`
-    sites: pairs on one founder agree for the whole stretch."""
-    cols = []
-    for k0 in range(0, V, stretch):
-        src = rng.integers(0, founders, n)
-        for _ in range(min(stretch, V - k0)):
-            fb = rng.integers(0, 2, founders)
-            cols.append([int(x) for x in fb[src]])
-    return cols
 
 
 # ---- CPU tests ---------------------------------------------------------------------------
@@ -331,77 +296,6 @@ def test_nsl_is_exported():
 
 
 # ---- GPU tests ---------------------------------------------------------------------------
-N_SITES = 32_000
-SHAPES = {   # name -> (samples, population masks): the shapes of test_rmin.py
-    "n12p2": (12, _blocks([6, 6])),                                   # 2-byte rows
-    "n24p3": (24, _blocks([8, 8, 8])),                                # 4-byte rows
-    "n40p2i": (40, [sum(1 << s for s in range(0, 40, 2)), sum(1 << s for s in range(1, 40, 2))]),   # 8-byte rows
-    "n96p4": (96, _blocks([24] * 4)),                                 # 16-byte rows
-    "n126p3": (126, _blocks([70, 50, 6])),                            # population 0 straddles the words: 2,415 pairs, one wave per workgroup
-    "n14one": (14, [0b00000000111111, 0b00000001000000, 0b11111100000000]),   # a population of one; sample 7 in none
-}
-WIDE = ("n40p2i", "n96p4", "n126p3")   # windows of up to 3,000 rows, so that the checker stays within seconds
-_shapes = {}
-
-
-def _params(n, masks, flag=0):
-    from popbam_amd import workload
-    params = workload.default_params(n, len(masks), flag=flag)
-    for i, m in enumerate(masks):
-        params.set_pop_mask(i, m)
-        params.pop_n[i] = bin(m).count("1")
-    return params
-
-
-def _shape(name):
-    """One called synthetic batch per shape, shared by the tests (read only)."""
-    if name not in _shapes:
-        import torch
-        from popbam_amd import _lib, workload
-        n, masks = SHAPES[name]
-        params = _params(n, masks)
-        ctx = _lib.Context(params, 0)
-        syn = workload.SynthPileup(ctx, N_SITES, 10, SEED + n)
-        hp = workload.HotPath(ctx, syn, [(0, N_SITES)], _lib.PBG_S_SFS)
-        hp.call()
-        ctx.sync_check()
-        torch.cuda.synchronize()
-        types, flags = harness.rows_to_sites(hp.rows.cpu().numpy(), ctx.row_bytes, N_SITES, n)
-        _shapes[name] = (ctx, params, hp.rows, types, flags)
-    return _shapes[name]
-
-
-def _windows(n_sites, whole):
-    """Windows from 3 rows up: overlapping, empty, beg == end, beg > end; the whole batch when asked."""
-    rng = np.random.default_rng(7)
-    wins = [(0, n_sites) if whole else (0, 3_000), (0, 2_000), (9_999, 12_001), (5, 5), (0, 1), (9, 4)]
-    for ln in (3, 10, 30, 60, 100, 150, 300, 1000, 3000):
-        for s in rng.integers(0, n_sites - ln, 2):
-            wins.append((int(s), int(s) + ln))
-    return wins
-
-
-def _run_nsl(ctx, rows, n_rows, wins, max_sites=0):
-    from popbam_amd import workload
-    j = workload.Nsl(ctx, len(wins), max_sites)
-    j(rows, _wins_tensor(wins), n_rows)
-    ctx.sync_check()
-    return _arrays(j, NAMES)
-
-
-def _run_sized(ctx, rows, n_rows, wins):
-    """The way the command line sizes the per-site arrays: the counts first, then max_sites = the largest."""
-    got = _run_nsl(ctx, rows, n_rows, wins, 0)
-    n_var = got[0]
-    assert got[1].shape == (len(wins), n_var.shape[1], 0) and got[3].shape == (len(wins), n_var.shape[1], 0, 2)
-    ms = int(n_var.max())
-    if ms == 0:
-        return got, 0
-    got = _run_nsl(ctx, rows, n_rows, wins, ms)
-    assert np.array_equal(got[0], n_var)
-    return got, ms
-
-
 def _check_against_ref(ctx, rows, types, flags, masks, wins, what=""):
     pop_n = [bin(m).count("1") for m in masks]
     got, ms = _run_sized(ctx, rows, len(flags), wins)
@@ -431,37 +325,6 @@ def test_nsl_matches_the_checker_on_called_rows(gpu_lib, name):
         assert m[w, i, :V].tolist() == [bin(ints[r] & masks[i]).count("1") for r in row[w, i, :V].tolist()]
     if name == "n14one":
         assert n_var[:, 1].max() == 0   # one sample: no variable site at all
-
-
-def _founder_types(rng, L, n, founders):
-    """Rows in which every sample copies one of a few founders (the copy changes every 64 rows): samples
-    on one founder are identical for the whole stretch (test_rmin.py's)."""
-    out = np.zeros((L, 2), np.uint64)
-    for r0 in range(0, L, 64):
-        src = rng.integers(0, founders, n)
-        fb = rng.integers(0, 2, (min(64, L - r0), founders))
-        sb = fb[:, src]   # [rows, n]
-        for s in range(n):
-            out[r0:r0 + len(sb), s >> 6] |= sb[:, s].astype(np.uint64) << np.uint64(s & 63)
-    return out if n > 64 else out[:, 0].copy()
-
-
-def _crafted(n, masks, types, flags):
-    """A context with the given population masks and device rows packed from (types, flags)."""
-    import torch
-    from popbam_amd import _lib
-    params = _params(n, masks)
-    ctx = _lib.Context(params, 0)
-    rows = torch.from_numpy(harness.rows_from_oracle(types, flags, ctx.row_bytes).copy()).cuda()
-    return ctx, params, rows
-
-
-def _padded(rows):
-    """The rows in a larger buffer of 0xFF bytes."""
-    import torch
-    big = torch.full((rows.numel() + 4096,), 0xFF, dtype=torch.uint8, device="cuda")
-    big[:rows.numel()] = rows
-    return big
 
 
 FOUNDER = [(12, 3, [6, 6]), (40, 4, [20, 20]), (96, 5, [48, 24, 24])]   # (samples, founders, population sizes)
@@ -636,101 +499,18 @@ def test_nsl_is_deterministic_and_interleaves_with_the_other_calls(gpu_lib):
     """Statistics, decay, nSL, joint spectrum, nSL, D statistics, the haplotype spectrum, Rmin, nSL,
     statistics, with the same pointers on one context and stream: each equals its own stand-alone run on
     a fresh context byte for byte, and two nSL runs give equal bytes."""
-    from popbam_amd import _lib, workload
-    n, npops, L = 12, 3, 64 * 500
-    wins = [(0, 6000)] + workload.reference_windows(0, L, 10_000) + [(s, s + 400) for s in range(0, 8000, 200)]
+    from popbam_amd import workload
     T = [(0, 1, 2), (0, 2, 1), (1, 2, 0)]
 
-    def fresh():
-        ctx = _lib.Context(workload.default_params(n, npops), 0)
-        syn = workload.SynthPileup(ctx, L, 10, SEED)
-        hp = workload.HotPath(ctx, syn, wins, _lib.PBG_S_ZNS)
-        hp.call()
-        ctx.sync_check()
-        return ctx, hp
+    def others(wins):
+        nw = len(wins)
+        return {"jsfs": (lambda ctx: workload.JointSfs(ctx, nw), ("cells", "diffs", "fst")),
+                "decay": (lambda ctx: workload.LdDecay(ctx, nw, 100, 100), ("pairs", "r2_sum", "n_var")),
+                "dstat": (lambda ctx: workload.DStat(ctx, nw, T), ("sums", "d", "fd", "fdm")),
+                "hfs": (lambda ctx: workload.Hfs(ctx, nw), workload.Hfs.NAMES),
+                "rmin": (lambda ctx: workload.Rmin(ctx, nw, 1, 16), workload.Rmin.NAMES)}
 
-    def zns(hp):
-        hp.out.t["ld_val"].fill_(-1.0)
-        hp.out.t["ld_snps"].fill_(-1)
-        hp.window_stats()
-
-    def zns_out(hp):
-        return hp.out.t["ld_snps"].cpu().numpy().tobytes(), hp.out.t["ld_val"].cpu().numpy().tobytes()
-
-    ctx, hp = fresh()
-    cnt = workload.Nsl(ctx, len(wins))(hp.rows, hp.wins, L)
-    ctx.sync_check()
-    MS = int(cnt.n_var.max().item())
-    assert MS > 20
-    ctx.close()
-    names_of = {"jsfs": ("cells", "diffs", "fst"), "decay": ("pairs", "r2_sum", "n_var"), "dstat": ("sums", "d", "fd", "fdm"),
-                "hfs": workload.Hfs.NAMES, "rmin": workload.Rmin.NAMES, "nsl": NAMES}
-    make = {"jsfs": lambda ctx: workload.JointSfs(ctx, len(wins)), "decay": lambda ctx: workload.LdDecay(ctx, len(wins), 100, 100),
-            "dstat": lambda ctx: workload.DStat(ctx, len(wins), T), "hfs": lambda ctx: workload.Hfs(ctx, len(wins)),
-            "rmin": lambda ctx: workload.Rmin(ctx, len(wins), 1, 16), "nsl": lambda ctx: workload.Nsl(ctx, len(wins), MS)}
-    alone = {}
-    ctx, hp = fresh()
-    zns(hp)
-    ctx.sync_check()
-    alone["zns"] = zns_out(hp)
-    ctx.close()
-    for key in make:
-        ctx, hp = fresh()
-        x = make[key](ctx)(hp.rows, hp.wins, L)
-        ctx.sync_check()
-        alone[key] = _arrays(x, names_of[key])
-        ctx.close()
-    assert alone["nsl"][3].max() > 0
-
-    ctx, hp = fresh()
-    zns(hp)
-    ctx.sync_check()
-    first = zns_out(hp)
-    order = ("decay", "nsl", "jsfs", "nsl", "dstat", "hfs", "rmin", "nsl")
-    ran = [(key, make[key](ctx)(hp.rows, hp.wins, L)) for key in order]
-    zns(hp)
-    ctx.sync_check()
-    assert first == alone["zns"] == zns_out(hp)
-    for key, x in ran:
-        for g, w_, nm in zip(_arrays(x, names_of[key]), alone[key], names_of[key]):
-            assert g.tobytes() == w_.tobytes(), (key, nm)
-    for k, drop in enumerate(NAMES):   # a NULL member: the others as before, the dropped array untouched
-        if drop == "row":
-            continue   # sl and cens need it
-        part = workload.Nsl(ctx, len(wins), MS)
-        getattr(part, drop).fill_(3)
-        setattr(part.out, drop, None)
-        part(hp.rows, hp.wins, L)
-        ctx.sync_check()
-        got = _arrays(part, NAMES)
-        for j, nm in enumerate(NAMES):
-            if j == k:
-                assert (got[j] == 3).all(), nm
-            else:
-                assert got[j].tobytes() == alone["nsl"][j].tobytes(), (drop, nm)
-    ctx.close()
-
-
-BOUNDS_SNIPPET = r"""
-import sys, numpy as np, torch
-sys.path.insert(0, {repo!r}); sys.path.insert(0, {repo!r} + "/tests")
-from popbam_amd import _lib, workload
-assert _lib.load().pbg_build_info() == b"bounds"
-params = workload.default_params({n}, {npops})
-for i, m in enumerate({masks!r}):
-    params.set_pop_mask(i, m)
-    params.pop_n[i] = bin(m).count("1")
-ctx = _lib.Context(params, 0)
-syn = workload.SynthPileup(ctx, {n_sites}, 10, {seed})
-hp = workload.HotPath(ctx, syn, {wins!r}, _lib.PBG_S_SFS)
-hp.call()
-ctx.sync_check()
-j = workload.Nsl.of(hp, {max_sites})
-ctx.sync_check()
-np.savez({out!r}, rows=hp.rows.cpu().numpy(), **{{k: getattr(j, k).cpu().numpy() for k in workload.Nsl.NAMES}})
-ctx.close()
-print("ok")
-"""
+    _interleaving("nsl", ("Nsl",), others, ("decay", "nsl", "jsfs", "nsl", "dstat", "hfs", "rmin", "nsl"))
 
 
 @pytest.mark.gpu
@@ -741,19 +521,14 @@ def test_nsl_under_the_bounds_build(gpu_lib, tmp_path, name):
         pytest.skip("the bounds build is not there (make bounds)")
     ctx, params, rows, types, flags = _shape(name)
     n, masks = SHAPES[name]
-    out = str(tmp_path / "bounds.npz")
-    env = dict(os.environ, POPBAM_GPU_LIB=BOUNDS_LIB)
     wins = _windows(N_SITES, False)
     pop_n = [bin(m).count("1") for m in masks]
     ints, seg = row_ints(types), (np.asarray(flags) & SEG) > 0
     ms = max(len(variable_sites(ints, seg, pm, n_i, a, b)) for a, b in wins if a < b for pm, n_i in zip(masks, pop_n))
-    r = subprocess.run([sys.executable, "-c", BOUNDS_SNIPPET.format(repo=REPO, n=n, npops=len(masks), masks=masks, n_sites=N_SITES,
-                                                                   seed=SEED + n, out=out, wins=wins, max_sites=ms)],
-                       env=env, capture_output=True, text=True, timeout=180)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
-    z = np.load(out)
-    assert np.array_equal(z["rows"], rows.cpu().numpy())
-    _assert_same(tuple(z[k] for k in NAMES), ref_nsl(types, flags, masks, pop_n, wins, ms), "bounds")
+    (brows, got), = _bounds_child(tmp_path, [dict(call="Nsl", n=n, masks=masks, wins=wins, n_rows=N_SITES, max_sites=ms,
+                                                  synth=(N_SITES, 10, SEED + n))])
+    assert np.array_equal(brows, rows.cpu().numpy())
+    _assert_same(got, ref_nsl(types, flags, masks, pop_n, wins, ms), "bounds")
 
 
 # ---- command lines -----------------------------------------------------------------------

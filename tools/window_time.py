@@ -25,7 +25,8 @@ A tree without one of the calls cannot run that pass; rmin, nsl, xpnsl and snn a
 named in `skipped`): rmin's yardstick is the decay_1x1 of the tree before it, nsl's is that tree's rmin,
 and with two trees of which the first has no nsl the comparison sets nsl_nvar against the first
 tree's rmin and gives nsl's ratio to it (when both trees have nsl, it is compared pass against pass
-like every other); xpnsl's yardsticks are the first tree's nsl_nvar and nsl, and the comparison gives the ratios;
+like every other); likewise the yardsticks of xpnsl are the nsl_nvar and nsl of a first tree without xpnsl, and the
+comparison gives the ratios;
 pairdiff's yardstick is the first tree's sfs, which streams the same rows; snn_1000 has no predecessor.
 
 Every --tree (default: this checkout) is measured in a fresh child process that imports that tree's
@@ -176,8 +177,8 @@ def compare(first, second):
                 new = statistics.mean(r[nm + "_ms_median"] for r in second)
                 cmp[nm] = {"first_rmin_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
         cmp["nsl_nvar"].update(margin_ms=round(margin, 4), ok=cmp["nsl_nvar"]["second_ms"] <= base + margin)
-    for nm, yard in (("xpnsl_nvar", "nsl_nvar"), ("xpnsl", "nsl")):   # xpnsl against the first tree's nsl
-        if yard + "_ms_median" in first[0] and nm + "_ms_median" in second[0]:
+    for nm, yard in (("xpnsl_nvar", "nsl_nvar"), ("xpnsl", "nsl")):   # xpnsl against the nsl of a first tree without xpnsl
+        if yard + "_ms_median" in first[0] and nm + "_ms_median" in second[0] and nm + "_ms_median" not in first[0]:
             base = statistics.mean(r[yard + "_ms_median"] for r in first)
             new = statistics.mean(r[nm + "_ms_median"] for r in second)
             cmp[nm] = {f"first_{yard}_ms": round(base, 4), "second_ms": round(new, 4), "ratio": round(new / base, 3)}
