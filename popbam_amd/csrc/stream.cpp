@@ -286,6 +286,11 @@ int window_list(pbg_ctx *c, const pbg_cmd &cmd, int64_t dpos0, uint32_t dsites,
         const void *d = wl.front().d;
         c->plans.erase(std::remove_if(c->plans.begin(), c->plans.end(), [&](const pbg_ctx::Plan &p) { return p.wins == d; }),
                        c->plans.end());
+        // pbg_window_ld_decay keys its validated lists on the same pointer: a later list that lands on the
+        // freed address with the same n_win and n_rows must be validated, and its pool need met, again
+        c->decay_plans.erase(std::remove_if(c->decay_plans.begin(), c->decay_plans.end(),
+                                            [&](const pbg_ctx::DecayPlan &p) { return p.wins == d; }),
+                             c->decay_plans.end());
         HIPCHK(c, hipFree(wl.front().d));
         wl.erase(wl.begin());
     }
